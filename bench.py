@@ -12,6 +12,13 @@ are already resident in HBM; the correlation matrix stays in HBM.  Work per GPU 
 the metric's unit (ordered sequence pairs): N_rows(G) = 50 000 * sqrt(G), so G=1 is
 BASELINE.json configs[1] (50k x 2 kb, k=6) and scaling is weak.  Rank 0 prints one JSON line.
 
+A plain run sets up, warms up, times `--steps` steps and prints the line (`value`, `ms_per_step`, and the
+roofline and per-kernel figures of the timed steps themselves).  `--full` adds what runs after the timed region:
+the check of r against the oracle (`verified`), the f16f8 arm, the CPU baseline, the 200 000-row target and the
+`e2e` record at N = 1; the all-reduced check and the opt-in chain A/B at N > 1.  `--dump-outputs DIR` writes
+what the last timed step computed (a seeded sample of rows of r and of the normalised counts, the column mean and
+std) to DIR/*.npy; the inputs are the same in every run with the same arguments.
+
 On G > 1 GPUs the default result layout is the symmetric one (seekr_amd/distributed.py): each
 unordered pair of row shards is multiplied once, by one of its two ranks, which keeps the
 block and its transpose; every ordered pair ends up in exactly one GPU's HBM, as on one GPU
@@ -67,7 +74,7 @@ def parse(argv=None):
     ap.add_argument("--precision", default=os.environ.get("SEEKR_PRECISION", "f16x3"),
                     choices=["fp32", "bf16x3", "f16x3", "f16f8"],
                     help="Pearson contraction arithmetic; every choice is inside the parity bar "
-                         "|dr| <= 2e-6 + 1e-5|r| (tests/test_gpu_parity.py) on the bench data; f16x3 carries float32-grade operands, bf16x3 is ~5 % faster")
+                         "|dr| <= 2e-6 + 1e-5|r| (tests/test_gpu_parity.py) on the bench data; f16x3 carries float32-grade operands, bf16x3 is ~5 %% faster")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-f16f8-arm", action="store_true", help="skip the opt-in two-product-unit contraction's extra measurement "
                     "after the timed region (f16f8_arm in the line)")
@@ -83,7 +90,17 @@ def parse(argv=None):
     ap.add_argument("--launch-timeout", type=float, default=300.0,
                     help="launcher mode: seconds after which the rank processes are killed")
     ap.add_argument("--no-selftest", action="store_true", help="skip the half-ring schedule's self-test before the warm-up")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the extras: the check of r against the oracle (verified; at N > 1 "
+                         "on every rank), the f16f8 arm, the CPU baseline, the 200 000-row target, the e2e record and (N > 1, "
+                         "opt-in) the chain A/B; without it a run sets up, warms up, times its steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32, < 64 MB in all; "
+                         "a fixed, seeded sample of rows): counts, mean, std, r (one GPU only)")
+    args = ap.parse_args(argv)
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1 (r is spread over the ranks' HBM at N > 1)")
+    return args
 
 
 # ------------------------------------------------------------------------------------ launcher ----
@@ -265,6 +282,24 @@ def verify_rows(ctx, r, x_norm, n_check=32, seed=1):
         if not np.isfinite(worst):
             return False, worst
     return worst <= 1.0, worst
+
+
+DUMP_BYTES = {"r": 48e6, "counts": 12e6}  # mean and std (4 B per column) take the rest of 64 MB
+
+
+def dump_outputs(out_dir, r, x, mean, std):
+    """What the last step computed, as a caller of the pipeline receives it (BasicCounter: counts, mean, std; pearson: r),
+    written as float32 .npy files: the column mean and std whole, and a fixed, seeded sample of rows (the same rows of the
+    normalised counts and of r, all columns of each; as many as fit in DUMP_BYTES, sorted)."""
+    n, n_cols = r.shape[1], x.shape[1]
+    n_rows = max(1, min(x.shape[0], int(DUMP_BYTES["r"] // (4 * n)), int(DUMP_BYTES["counts"] // (4 * n_cols))))
+    rows = np.sort(np.random.default_rng([SEED, 7]).choice(x.shape[0], n_rows, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"counts": np.stack([x.to_numpy(int(i), 1).reshape(-1) for i in rows]),
+              "r": np.stack([r.to_numpy(int(i), 1).reshape(-1) for i in rows]),
+              "mean": mean.vector(), "std": std.vector()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def end_to_end(ctx, k, length, n_seqs, precision):
@@ -637,14 +672,19 @@ def run_rank(args):
     use_allgather = args.layout == "allgather" and size > 1
     recv = [engine.empty_operand(max_shard, n_cols) for _ in range(n_recv)] if size > 1 and not use_allgather else [None, None]
     gathered = engine.empty_operand(n_total, n_cols) if use_allgather else None  # every rank's operand rows, kept between steps
+    stats = []  # --dump-outputs: the column mean and std of the last step (released when the next step starts)
 
     def step():
+        stats.clear()
         if generic:
             _lib.count_generic_dev(ctx, packed, args.alphabet, k, out=x)
         else:
             _lib.count_per_kb(ctx, packed, k, out=x)
         # column statistics (rank-chained), then ONE pass: normalised counts -> x, standardised rows -> z
-        zz = sharded_normalize_prepare(engine, comm, x, n_total, "Log2.post", True, True, keep_counts=True, op=z)[3]
+        center, scale, _, zz = sharded_normalize_prepare(engine, comm, x, n_total, "Log2.post", True, True, keep_counts=True, op=z)
+        if args.dump_outputs:
+            stats.extend((center, scale))
+        del center, scale
         if symmetric_layout:
             sharded_pearson_symmetric(engine, comm, zz, bounds, r, r_col, recv, grouped=args.grouped_shifts)
         elif use_allgather:
@@ -672,6 +712,8 @@ def run_rank(args):
     ctx.prof_enable(False)
     elapsed = comm.allreduce([elapsed], "max")[0]
     beat("after the timed region (per-rank statistics, verification)")
+    if args.dump_outputs:  # before anything below reuses x or r (the f16f8 arm does)
+        dump_outputs(args.dump_outputs, r, x, *stats)
 
     # ---- per-kernel device times of the timed region (HIP events on the ctx stream; comm_* on the communication stream)
     kern = exclusive_kernel_times(ctx)
@@ -707,7 +749,7 @@ def run_rank(args):
                     "(serial by construction: rank g waits for ranks < g); with column_sum_chain = peer mailboxes that wait happens "
                     "inside the column-sum kernels (colsum_ms: rank g's kernels are resident and waiting while ranks < g walk)"}
     multi_verified = None
-    if size > 1:
+    if size > 1 and args.full:
         # correctness probe on EVERY rank, outside the timed region: 8 random rows of the rank's own diagonal block of the
         # r this run produced against the oracle on the rank's host copy of its normalised counts (the block needs no other
         # rank's rows; the cross blocks are covered by the schedule's self-test and the mirror checks); verdict all-reduced
@@ -730,7 +772,7 @@ def run_rank(args):
             del x_loc
         multi_verified = comm.allreduce([worst], "max")[0]
     chain_ab = None
-    if size > 1 and os.environ.get("SEEKR_BENCH_CHAIN_AB") == "1":
+    if size > 1 and args.full and os.environ.get("SEEKR_BENCH_CHAIN_AB") == "1":
         beat("chain A/B (opt-in)")
         try:
             chain_ab = column_chain_ab(ctx, comm, engine, x, n_cols)
@@ -849,12 +891,14 @@ def run_rank(args):
             out["chain_ab"] = chain_ab
         out["selftest"] = ("skipped" if args.no_selftest or not symmetric_layout
                            else "half-ring schedule == row-block schedule on a small set, on every rank")
+    if multi_verified is not None:
         out["verified"] = bool(multi_verified <= 1.0)
         out["verified_detail"] = {"rows": "8 per rank", "columns": "the rank's own diagonal block", "worst_error_over_bar": round(multi_verified, 4),
                                   "bar": "|dr| <= 2e-6 + 1e-5 |r| against oracle.pearson (pearson.py:35-41) on every rank, all-reduced"}
     if os.environ.get("SEEKR_BENCH_FALLBACK"):
         out["layout_fallback"] = os.environ["SEEKR_BENCH_FALLBACK"]
-    if size == 1:
+    # the extras below run with --full only (a plain run prints the line as it stands)
+    if size == 1 and args.full:
         # correctness probe of the r this run produced, outside the timed region: 32 random rows x all columns
         # against the oracle on the host copy of the normalised counts (x holds them: keep_counts=True)
         x_host = x.to_numpy()
@@ -862,7 +906,7 @@ def run_rank(args):
         out["verified"] = bool(ok)
         out["verified_detail"] = {"rows": min(32, n_loc), "columns": n_total, "worst_error_over_bar": round(worst, 4),
                                   "bar": "|dr| <= 2e-6 + 1e-5 |r| against oracle.pearson (pearson.py:35-41)"}
-    if size == 1 and args.precision == "f16x3" and not generic and k in (6, 7) and not args.no_symmetry and not args.no_f16f8_arm:
+    if size == 1 and args.full and args.precision == "f16x3" and not generic and k in (6, 7) and not args.no_symmetry and not args.no_f16f8_arm:
         # The opt-in two-product-unit contraction (SKR_PREC_F16F8), measured in the same run AFTER the timed
         # region and never part of `value`: the same step with the other operand layout, the same number of steps,
         # the same verification against the oracle.
@@ -900,7 +944,7 @@ def run_rank(args):
                     "product-units per k instead of 3); measured after the timed region, never part of `value`; operand_kind 3 = "
                     "the fp8 cross layout was kept, 2 = the fill routed these rows back to the three-product split"}
         z8.free()
-    if size == 1 and not args.no_cpu_baseline and not generic:
+    if size == 1 and args.full and not args.no_cpu_baseline and not generic:
         head = x_host[:min(12000 if k <= 6 else 4000, n_loc)]
         cb = cpu_baseline(k, length, head)
         t_cpu = n_total * length / cb["rate_bases"] + pairs_per_step / cb["rate_pairs"]

@@ -24,7 +24,7 @@ def test_bench_line_carries_the_measurement_contract():
     probe and the PCIe-inclusive e2e block — and a verified = true r."""
     import json
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "6000", "--length", "600", "--steps", "2",
-                          "--warmup", "1"], capture_output=True, text=True, timeout=900)
+                          "--warmup", "1", "--full"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -46,12 +46,42 @@ def test_bench_line_carries_the_measurement_contract():
     assert "never part of `value`" in arm["note"] and d["config"]["precision"] == "f16x3"
 
 
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    """bench.py without --full: the headline line and nothing after the timed region; --dump-outputs writes the last step's
+    outputs as float32 .npy files under 64 MB, and the sampled rows of r are the Pearson r of the sampled rows of the
+    normalised counts (the columns of r at those same rows, against the oracle)."""
+    import json
+    import numpy as np
+    import bench
+    from oracle import seekr_oracle as orc
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "6000", "--length", "600", "--steps", "2",
+                          "--warmup", "1", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline", "roofline_count"):
+        assert key in d, key
+    assert d["steps"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+    for key in ("verified", "cpu_baseline", "e2e", "f16f8_arm", "target_200k"):
+        assert key not in d, key
+    got = {name: np.load(str(tmp_path / (name + ".npy"))) for name in ("counts", "mean", "std", "r")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert sum(os.path.getsize(str(tmp_path / (name + ".npy"))) for name in got) <= 64e6
+    counts, r = got["counts"], got["r"]
+    assert got["mean"].shape == got["std"].shape == (4096,) and counts.shape[1] == 4096 and r.shape == (counts.shape[0], 6000)
+    assert np.isfinite(got["mean"]).all() and np.isfinite(got["std"]).all() and np.isfinite(counts).all()
+    rows = np.sort(np.random.default_rng([bench.SEED, 7]).choice(6000, counts.shape[0], replace=False))
+    want = orc.pearson(counts, counts)
+    assert np.all(np.abs(r[:, rows] - want) <= 2e-6 + 1e-5 * np.abs(want))
+
+
 def test_bench_line_prices_an_output_bound_contraction_against_hbm():
     """At k = 4 (256 columns) writing r (4 B per pair) takes longer at 8 TB/s than 512 flop per pair take at the dense
     matrix-core peak: `roofline.bound` says "hbm", achieved / peak are GB/s, the matrix-core view is kept next to it."""
     import json
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--k", "4", "--rows", "6000", "--length", "600", "--steps", "2",
-                          "--warmup", "1", "--no-cpu-baseline", "--no-target-200k", "--no-f16f8-arm"], capture_output=True, text=True, timeout=900)
+                          "--warmup", "1", "--full", "--no-cpu-baseline", "--no-target-200k", "--no-f16f8-arm"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
     rf = d["roofline"]

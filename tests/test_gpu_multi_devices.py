@@ -179,7 +179,7 @@ def test_bench_reports_the_host_to_host_figures_with_seekr_devices(tmp_path):
     env = dict(os.environ, SEEKR_TEST_HOOKS="1", SEEKR_BENCH_E2E_DEVICES="0,0", SEEKR_TRANSPORT="peer")
     env.pop("SEEKR_DEVICES", None)
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--rows", "6000", "--length", "600", "--steps", "2", "--warmup", "1",
-                          "--no-f16f8-arm"], env=env, capture_output=True, text=True, timeout=600)
+                          "--full", "--no-f16f8-arm"], env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
     dev = out["e2e"]["seekr_devices_all"]

@@ -137,7 +137,7 @@ def test_bench_under_torchrun_with_two_ranks(mock_lib):
     env = dict(os.environ, SEEKR_TEST_HOOKS="1", SEEKR_RCCL_LIB=mock_lib, SEEKR_FORCE_DEVICE="0", MOCK_RCCL_ASYNC="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--rows", "6000", "--length", "500"]
+           "--rows", "6000", "--length", "500", "--full"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -194,7 +194,7 @@ def test_bench_starts_its_own_rank_processes(mock_lib):
     carries n_ranks_seen and the per-rank transfer / exposed-wait times."""
     import json
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--rows", "6000",
-           "--length", "500"]
+           "--length", "500", "--full"]
     res = subprocess.run(cmd, env=_launcher_env(mock_lib), capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -232,7 +232,7 @@ def test_eight_ranks_at_the_drivers_weak_scaling_size(layout, mock_lib):
     if free_hbm < 200 or free_shm < 24:
         pytest.skip("needs 200 GB of free HBM and 24 GB of /dev/shm (have %.0f / %.0f)" % (free_hbm, free_shm))
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1", "--layout", layout,
-           "--launch-timeout", "900"]
+           "--launch-timeout", "900", "--full"]
     env = _launcher_env(mock_lib, SEEKR_BENCH_CHAIN_AB="1", SEEKR_CHAIN_HOST_WAIT="1")
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1200)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-6000:]
@@ -278,7 +278,7 @@ def test_the_strong_scaling_spelling_of_the_scale_command(mock_lib):
     says "strong" and carries the same contract.  R = 60 000 here (eight rank processes share this one GPU)."""
     import json
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--rows", "60000", "--steps", "2", "--warmup", "1",
-           "--launch-timeout", "600"]
+           "--launch-timeout", "600", "--full"]
     res = subprocess.run(cmd, env=_launcher_env(mock_lib), capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-6000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])

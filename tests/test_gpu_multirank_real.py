@@ -69,7 +69,7 @@ def test_bench_reports_the_chain_ab_between_two_real_gpus():
                                                                "SEEKR_TEST_HOOKS", "SEEKR_RCCL_LIB", "SEEKR_FORCE_DEVICE", "SEEKR_CHAIN")}
     env["SEEKR_BENCH_CHAIN_AB"] = "1"  # opt-in since round 5: a hang in the A/B must not cost the headline line
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--rows", "12000",
-           "--length", "500"]
+           "--length", "500", "--full"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])

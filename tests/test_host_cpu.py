@@ -182,6 +182,19 @@ def _bench():
     return importlib.import_module("bench")
 
 
+def test_bench_extras_are_opt_in_and_dumps_take_one_gpu():
+    """A plain bench.py run leaves the extras out (--full brings them); --dump-outputs is refused at N > 1, where r is
+    spread over the ranks, before any rank starts."""
+    bench = _bench()
+    args = bench.parse(["--gpus", "1", "--steps", "4", "--warmup", "2"])
+    assert args.full is False and args.dump_outputs is None and args.steps == 4
+    args = bench.parse(["--full", "--dump-outputs", "out"])
+    assert args.full is True and args.dump_outputs == "out"
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dump-outputs", "out"],
+                         capture_output=True, text=True, timeout=60)
+    assert res.returncode == 2 and "--dump-outputs needs --gpus 1" in res.stderr and res.stdout == ""
+
+
 def test_bench_launcher_reports_every_rank_and_retries_once():
     """`python bench.py --gpus 2` without WORLD_SIZE starts its own rank processes.  Here there is no
     GPU (or, on a test box, one): both attempts fail, and the launcher must say so loudly — non-zero exit, every

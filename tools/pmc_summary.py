@@ -32,7 +32,7 @@ for path in sorted(glob.glob(os.path.join(out_dir, "pmc*", "**", "*counter_colle
             cell[0] += float(row["Counter_Value"])
             cell[1] += 1
 if is_bench:
-    print("# rocprofv3 --pmc passes (separate runs, --kernel-trace only) of: python3 bench.py --steps 2 --warmup 1 "
+    print("# rocprofv3 --pmc passes (separate runs, --kernel-trace only) of: python3 bench.py --steps 2 --warmup 1 --full "
           "--no-cpu-baseline --precision {} {}".format(prec, " ".join(extra)).rstrip())
     # what bench.py's pmc_traffic() matches before it quotes a number from this file
     generic = not (len(b_args.alphabet) == 4 and len(set(b_args.alphabet)) == 4)

@@ -18,7 +18,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 # shellcheck disable=SC2086
 timeout -k 10 $T_TRACE rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o "$TAG" -- \
-    python3 "$REPO/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --precision "$PREC" $EXTRA \
+    python3 "$REPO/bench.py" --steps 5 --warmup 2 --full --no-cpu-baseline --precision "$PREC" $EXTRA \
     > "$OUT/${TAG}_bench_under_rocprof.json" 2> "$OUT/trace.err"
 i=0
 for group in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY" \
@@ -28,7 +28,7 @@ for group in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_AN
     i=$((i + 1))
     # shellcheck disable=SC2086
     timeout -k 10 $T_PMC rocprofv3 --kernel-trace --pmc $group --output-format csv -d "$OUT/pmc$i" -o "$TAG" -- \
-        python3 "$REPO/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --precision "$PREC" $EXTRA \
+        python3 "$REPO/bench.py" --steps 2 --warmup 1 --full --no-cpu-baseline --precision "$PREC" $EXTRA \
         > "$OUT/pmc$i.json" 2> "$OUT/pmc$i.err"
 done
 cd "$REPO"
