@@ -370,8 +370,8 @@ int skr_pearson(skr_ctx* ctx, const skr_mat* counts1, const skr_mat* counts2, in
 /* In place: r[r < cutoff] = 0 (NaN stays), then the diagonal r[i, i + diag_col0] = 0
  * (kmer_leiden.py:94-96; diag_col0 places the diagonal inside a row block).                 */
 int skr_threshold_zero_diag(skr_ctx* ctx, skr_mat* r, float cutoff, int64_t diag_col0);
-/* out = r[np.triu_indices(n, k)] for a square float32 r (find_dist.py:163 uses k = 1);
- * out holds (n-k)(n-k+1)/2 values.                                                           */
+/* out = r[np.triu_indices(n, k)] for a square float32 or float64 r (find_dist.py:163 uses k = 1);
+ * out has r's dtype and holds (n-k)(n-k+1)/2 values.                                        */
 int skr_triu_flatten(skr_ctx* ctx, const skr_mat* r, int64_t k, skr_mat* out);
 /* out_host[i] = src.flat[idx_host[i]] — the device side of np.random.choice(values, size,
  * replace=False) (find_dist.py:169): the host draws the indices with numpy's generator.     */
@@ -385,6 +385,35 @@ int skr_empirical_pvalues(skr_ctx* ctx, const skr_mat* r, const skr_mat* sorted_
  * tuple find_dist returns.  Evaluated in float64 like scipy; other names: SKR_ERR_UNSUPPORTED.                */
 int skr_parametric_pvalues(skr_ctx* ctx, const skr_mat* r, const char* dist_name, const double* params, int n_params,
                            skr_mat* p);
+
+/* ---------------------------------------------------------------- multiple-testing correction -- */
+/* methods of statsmodels 0.12.2 multipletests (adj_pval.py:53-138); SKR_ADJ_FDR_GBS is accepted as the reference
+ * passes any name through                                                                                        */
+enum {
+    SKR_ADJ_BONFERRONI = 0,
+    SKR_ADJ_SIDAK = 1,
+    SKR_ADJ_HOLM_SIDAK = 2,
+    SKR_ADJ_HOLM = 3,
+    SKR_ADJ_SIMES_HOCHBERG = 4,
+    SKR_ADJ_HOMMEL = 5,
+    SKR_ADJ_FDR_BH = 6,
+    SKR_ADJ_FDR_BY = 7,
+    SKR_ADJ_FDR_TSBH = 8,
+    SKR_ADJ_FDR_TSBKY = 9,
+    SKR_ADJ_FDR_GBS = 10
+};
+/* *symmetric = 1 when the float32 / float64 matrix p is square and, off the diagonal, round(x, 5) in p's dtype equals
+ * its mirror cell with NaN equal to NaN (is_symmetric, adj_pval.py:57-63).  Values only: the caller compares the
+ * row and column labels.                                                                                          */
+int skr_pvals_symmetric(skr_ctx* ctx, const skr_mat* p, int* symmetric);
+/* multipletests(tests, alpha, method)[1] written back into the matrix layout.  upper_only = 1: the tests are the
+ * strict upper triangle of the square p in np.triu_indices order and out is an [N, N] float64 matrix, NaN outside
+ * that triangle; upper_only = 0: the tests are all of p, row-major, and out has p's shape and the method's dtype
+ * (p's dtype for bonferroni, sidak and hommel, float64 otherwise).  Bit-exact with numpy except sidak's float32
+ * power (evaluated in float64, rounded once) and the holm-sidak power (device float64 pow); tied negative
+ * p-values are outside the contract.  No tests: SKR_ERR_ZERODIV; hommel above 2^22 tests: SKR_ERR_UNSUPPORTED;
+ * a workspace larger than the free device memory: SKR_ERR_NOMEM with the bytes needed.                       */
+int skr_adjust_pvalues(skr_ctx* ctx, const skr_mat* p, int method, double alpha, int upper_only, skr_mat* out);
 
 /* The non-zero cells that kmer_leiden.py:94-96 leaves in a block of r, as an edge list and
  * without writing the zeros: cells of r[0:nrows, col_begin:col_end] with !(v < cutoff) (NaN

@@ -115,6 +115,8 @@ SIGNATURES = {
     "skr_gather_f32": (_int, [_p, _p, _p, _i64, _p]),
     "skr_empirical_pvalues": (_int, [_p, _p, _p, _i64, _p]),
     "skr_parametric_pvalues": (_int, [_p, _p, C.c_char_p, C.POINTER(C.c_double), _int, _p]),
+    "skr_pvals_symmetric": (_int, [_p, _p, C.POINTER(_int)]),
+    "skr_adjust_pvalues": (_int, [_p, _p, _int, C.c_double, _int, _p]),
     "skr_edges": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, C.c_float, _int, _p, _p, _p, C.POINTER(_i64)]),
     "skr_pearson_gemm_edges": (_int, [_p, _p, _p, _p, _i64, _i64, C.c_float, _int, _p, _p, _p, C.POINTER(_i64)]),
     "skr_pearson_gemm_edges_needs_scratch": (_int, [_p, _p, _p, C.POINTER(_int)]),

@@ -1,5 +1,5 @@
-"""`seekr_kmer_counts`, `seekr_pearson`, `seekr_norm_vectors` with the reference's flags
-(console_scripts.py:564-681).  Only the three commands on the hot path are provided."""
+"""`seekr_kmer_counts`, `seekr_pearson`, `seekr_norm_vectors` and `seekr_adj_pval` with the reference's flags
+(console_scripts.py:564-681, 887-918).  Only the commands on the hot path are provided."""
 import argparse
 import sys
 
@@ -33,6 +33,21 @@ Examples
 --------
     labelled CSV in and out:   seekr_pearson counts.csv counts.csv -o r.csv
     .npy in and out:           seekr_pearson counts.npy counts.npy -o r.npy -bi -bo
+"""
+
+ADJ_PVAL_DOC = """
+Description
+-----------
+Multiple-testing correction of a labelled p-value CSV (the output of find_pval) on an MI355X,
+with statsmodels' multipletests methods.  A symmetric matrix (same row and column names, the
+same values on both sides of the diagonal to 5 decimals) is corrected over its upper triangle
+only and the rest of the output is empty; any other matrix is corrected as a whole.  Flags and
+output file are those of the reference command of the same name.
+
+Examples
+--------
+    Bonferroni at 0.05, written to adj.csv:   seekr_adj_pval pvals.csv bonferroni -a 0.05 -o adj
+    Benjamini-Hochberg, not saved:            seekr_adj_pval pvals.csv fdr_bh
 """
 
 NORM_VECTORS_DOC = """
@@ -145,3 +160,30 @@ def console_norm_vectors():
     parser.add_argument("-k", "--kmer", default=6, help="k, the word length.")
     args = _parse_args_or_exit(parser)
     _run_norm_vectors(args.fasta, args.mean_vector, args.std_vector, args.log2, int(args.kmer))
+
+
+def _read_pval_csv(path):
+    """pd.read_csv(path, header=0, index_col=0) (console_scripts.py:913): natively when the file is in the subset the
+    native reader reproduces (an empty corner cell, text row labels, distinct column labels), else through pandas."""
+    import pandas as pd
+    with open(path, "rb") as f:
+        corner_empty = f.read(1) == b","
+    native = _lib.load_csv_labelled(path) if corner_empty else None
+    if native is None:
+        return pd.read_csv(path, header=0, index_col=0)
+    values, rows, cols = native
+    return pd.DataFrame(values, index=pd.Index(rows, dtype=object), columns=pd.Index(cols, dtype=object))
+
+
+def console_adj_pval():
+    from seekr_amd import adj_pval
+    parser = argparse.ArgumentParser(usage=ADJ_PVAL_DOC, formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    parser.add_argument("pval_path", help="Labelled CSV of the p-values to correct (find_pval's output).")
+    parser.add_argument("method", help=("Correction method: bonferroni, sidak, holm-sidak, holm, simes-hochberg, hommel, "
+                                        "fdr_bh, fdr_by, fdr_tsbh, fdr_tsbky (statsmodels' multipletests names)."))
+    parser.add_argument("-a", "--alpha", default=0.05, help="Family-wise error rate (only the two-stage FDR methods use it).")
+    parser.add_argument("-o", "--outputname", default=None,
+                        help="Where the corrected matrix goes ('.csv' is appended); not saved when omitted.")
+    args = _parse_args_or_exit(parser)
+    pvals = _read_pval_csv(args.pval_path)
+    adj_pval.adj_pval(pvals, args.method, float(args.alpha), args.outputname)

@@ -7,6 +7,7 @@ it: keeping these reductions on the GPU avoids shipping an N x N m
     empirical_pvalues     find_pval.py:158-164   p[i,j] = np.sum(fitres > sim[i,j]) / len(fitres)
     edges / pearson_edges kmer_leiden.py:91-96   the thresholded matrix as an edge list, r produced and consumed
                                                  one row stripe at a time (N x N never exists)
+    adjust_pvalues        adj_pval.py:53-138     multipletests on the p-value matrix (symmetric: upper triangle)
 
 Every function takes and returns device matrices (`seekr_amd._lib.Matrix`); `*_host` helpers
 wrap host arrays for drop-in use.
@@ -26,10 +27,10 @@ def threshold_zero_diag(r, cutoff, diag_col0=0):
 
 
 def triu_values(r, k=1):
-    """1 x (n-k)(n-k+1)/2 device vector in np.triu_indices order."""
+    """1 x (n-k)(n-k+1)/2 device vector in np.triu_indices order (float32 or float64, r's dtype)."""
     n = r.rows
     m = max(0, n - k)
-    out = r.ctx.empty(1, m * (m + 1) // 2)
+    out = r.ctx.empty(1, m * (m + 1) // 2, r.dtype)
     _lib.check(_lib.lib().skr_triu_flatten(r.ctx._h, r._h, int(k), out._h))
     return out
 
@@ -239,3 +240,59 @@ def pearson_edges(z, cutoff, stripe_rows=8192, upper_only=True, engine_gemm=None
     if buf is not None:
         buf.free()
     return tuple(np.concatenate(p) if p else np.empty(0) for p in out)
+
+
+ADJ_METHODS = {"bonferroni": 0, "sidak": 1, "holm-sidak": 2, "holm": 3, "simes-hochberg": 4, "hommel": 5, "fdr_bh": 6,
+               "fdr_by": 7, "fdr_tsbh": 8, "fdr_tsbky": 9, "fdr_gbs": 10}
+_ADJ_ALIASES = {"bonferroni": ["b", "bonf"], "sidak": ["s"], "holm-sidak": ["hs"], "holm": ["h"], "simes-hochberg": ["sh"],
+                "hommel": ["ho"], "fdr_bh": ["fdr_i", "fdr_p", "fdri", "fdrp"], "fdr_by": ["fdr_n", "fdr_c", "fdrn", "fdrcorr"],
+                "fdr_tsbh": ["fdr_2sbh"], "fdr_tsbky": ["fdr_2sbky", "fdr_twostage"], "fdr_gbs": []}
+ADJ_ALIASES = {a: name for name, more in _ADJ_ALIASES.items() for a in [name] + more}
+HOMMEL_LIMIT = 1 << 22
+
+
+def adjust_method(method):
+    """The canonical multipletests name of `method` (aliases, any letter case); ValueError('method not recognized')."""
+    name = ADJ_ALIASES.get(str(method).lower())
+    if name is None:
+        raise ValueError("method not recognized")
+    return name
+
+
+def adjust_out_dtype(method, dtype, symmetric):
+    """dtype of adj_pval's result: float64, or the input dtype for bonferroni, sidak and hommel on the whole matrix."""
+    if not symmetric and adjust_method(method) in ("bonferroni", "sidak", "hommel"):
+        return np.dtype(dtype)
+    return np.dtype(np.float64)
+
+
+def check_hommel(method, n_tests):
+    if adjust_method(method) == "hommel" and n_tests > HOMMEL_LIMIT:
+        raise NotImplementedError("hommel on the device is limited to {} tests; this matrix has {}".format(HOMMEL_LIMIT,
+                                                                                                          n_tests))
+
+
+def pvals_symmetric(p):
+    """is_symmetric's value test of the device matrix p (square; off the diagonal round(x, 5) equals its mirror)."""
+    flag = C.c_int(0)
+    _lib.check(_lib.lib().skr_pvals_symmetric(p.ctx._h, p._h, C.byref(flag)))
+    return bool(flag.value)
+
+
+def adjust_pvalues(p, method, alpha=0.05, symmetric=None):
+    """multipletests(tests, alpha, method)[1] of the device matrix p (float32 or float64), left on the device: the
+    tests are the strict upper triangle when p is symmetric (an [N, N] float64 result, NaN elsewhere), else all of p
+    (p's shape, the method's dtype).  symmetric=None tests the values (skr_pvals_symmetric); labels are the caller's.
+    Bit-exact with statsmodels 0.12.2 except sidak's float32 power (evaluated in float64 and rounded once: numpy's
+    float32 power is not correctly rounded) and holm-sidak's float64 power (device pow, within a few ulp); tied
+    negative p-values are outside the contract (numpy's unstable argsort decides those)."""
+    name = adjust_method(method)
+    if symmetric is None:
+        symmetric = pvals_symmetric(p)
+    symmetric = bool(symmetric) and p.rows == p.cols
+    n_tests = p.rows * (p.rows - 1) // 2 if symmetric else p.rows * p.cols
+    check_hommel(name, n_tests)
+    out = p.ctx.empty(p.rows, p.cols, adjust_out_dtype(name, p.dtype, symmetric))
+    _lib.check(_lib.lib().skr_adjust_pvalues(p.ctx._h, p._h, ADJ_METHODS[name], C.c_double(float(alpha)),
+                                             1 if symmetric else 0, out._h))
+    return out

@@ -24,17 +24,18 @@ __global__ __launch_bounds__(256) void threshold_zero_diag_kernel(float* __restr
 }
 
 // out[start(i) + (j - i - k)] = r[i, j] for j >= i + k, start(i) = number of selected cells in rows < i:
-// exactly the order of np.triu_indices(n, k).  One workgroup per row segment, coalesced copies.
-__global__ __launch_bounds__(256) void triu_flatten_kernel(const float* __restrict__ r, int64_t n, int64_t k,
-                                                           float* __restrict__ out) {
+// exactly the order of np.triu_indices(n, k).  One workgroup per row segment, coalesced copies.  float32 / float64.
+template <typename T>
+__global__ __launch_bounds__(256) void triu_flatten_kernel(const T* __restrict__ r, int64_t n, int64_t k,
+                                                           T* __restrict__ out) {
     for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
         const int64_t first = i + k;
         if (first >= n) continue;
         // cells selected in rows 0..i-1: sum_{t<i} max(0, n - t - k)
         const int64_t full = std::min<int64_t>(i, std::max<int64_t>(0, n - k));
         const int64_t start = full * (n - k) - full * (full - 1) / 2;
-        const float* src = r + (size_t)i * n + first;
-        float* dst = out + start;
+        const T* src = r + (size_t)i * n + first;
+        T* dst = out + start;
         for (int64_t c = threadIdx.x; c < n - first; c += blockDim.x) dst[c] = src[c];
     }
 }
@@ -332,7 +333,8 @@ extern "C" int skr_threshold_zero_diag(skr_ctx* ctx, skr_mat* r, float cutoff, i
 
 extern "C" int skr_triu_flatten(skr_ctx* ctx, const skr_mat* r, int64_t k, skr_mat* out) {
     SKR_REQUIRE(ctx && r && out && r->ctx == ctx && out->ctx == ctx, "NULL argument or foreign ctx");
-    SKR_REQUIRE(r->dtype == SKR_F32 && out->dtype == SKR_F32, "float32 only");
+    SKR_REQUIRE((r->dtype == SKR_F32 || r->dtype == SKR_F64) && out->dtype == r->dtype,
+                "float32 or float64, out of the same dtype as r");
     SKR_REQUIRE(r->rows == r->cols, "triu needs a square matrix");
     SKR_REQUIRE(k >= 0, "k must be >= 0");
     const int64_t n = r->rows, m = std::max<int64_t>(0, n - k);
@@ -340,8 +342,13 @@ extern "C" int skr_triu_flatten(skr_ctx* ctx, const skr_mat* r, int64_t k, skr_m
     SKR_TRY(skr_activate(ctx));
     if (m == 0) return SKR_OK;
     SkrProfScope prof(ctx, "triu_flatten");
-    hipLaunchKernelGGL(triu_flatten_kernel, dim3((unsigned)std::min<int64_t>(n, (int64_t)ctx->num_cu * 16)), dim3(256), 0,
-                       ctx->stream, (const float*)r->data, n, k, (float*)out->data);
+    const dim3 grid((unsigned)std::min<int64_t>(n, (int64_t)ctx->num_cu * 16));
+    if (r->dtype == SKR_F64)
+        hipLaunchKernelGGL(triu_flatten_kernel<double>, grid, dim3(256), 0, ctx->stream, (const double*)r->data, n, k,
+                           (double*)out->data);
+    else
+        hipLaunchKernelGGL(triu_flatten_kernel<float>, grid, dim3(256), 0, ctx->stream, (const float*)r->data, n, k,
+                           (float*)out->data);
     SKR_HIP(hipGetLastError());
     return SKR_OK;
 }

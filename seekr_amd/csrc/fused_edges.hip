@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "radix.hpp"
 
 namespace {
 
@@ -15,11 +16,10 @@ namespace {
 // LSD radix sort of (key = row << 32 | column, value) pairs, 8 bits per pass, only over the bits that can be set:
 // ceil(bits(N) / 8) passes over the column field, then ceil(bits(M) / 8) over the row field (rows taken relative to
 // the block's first row).  One pass = digit histogram per chunk -> exclusive scan of the [256][chunks] table ->
-// stable scatter.  A chunk belongs to ONE wave, which walks it slice by slice (64 keys): the lanes holding the same
-// digit find each other with eight ballots (one per digit bit), a lane's place is the chunk's running count of its
-// digit plus the number of lower lanes in its group — stable by construction, no atomics, no cross-wave ranking.
+// stable scatter, with the wave-ballot ranking of radix.hpp.
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int kDigits = 256;
+using skr_radix::kDigits;
+using skr_radix::same_digit;
 
 struct RadixArgs {
     const unsigned long long* keys_in;
@@ -40,17 +40,6 @@ struct RadixArgs {
 __device__ __forceinline__ uint32_t digit_of(unsigned long long key, const RadixArgs& a) {
     const uint32_t f = a.row_field ? (uint32_t)(key >> 32) - a.row0 : (uint32_t)key;
     return (f >> a.shift) & (kDigits - 1);
-}
-
-// lanes of the wave that hold the same 8-bit digit as this one (all 64 lanes take part; `live` lanes only match live ones)
-__device__ __forceinline__ unsigned long long same_digit(uint32_t d, bool live) {
-    unsigned long long peers = __ballot(live);
-#pragma unroll
-    for (int b = 0; b < 8; b++) {
-        const unsigned long long ones = __ballot(live && ((d >> b) & 1u));
-        peers &= ((d >> b) & 1u) ? ones : ~ones;
-    }
-    return peers;
 }
 
 __global__ __launch_bounds__(64) void radix_count_kernel(const RadixArgs a) {
@@ -107,88 +96,8 @@ __global__ __launch_bounds__(64) void radix_scatter_kernel(const RadixArgs a) {
     }
 }
 
-// ---- exclusive prefix sum of a uint32 array in place (any length): block totals -> recursive scan of the totals ->
-// local scan with the block's offset.  4 096 elements per 256-thread block.
-constexpr int kScanBlock = 256, kScanPer = 16, kScanTile = kScanBlock * kScanPer;
-
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* lds, uint32_t* total) {
-    // wave scan, then the four wave totals
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) lds[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kScanBlock / 64; w++) {
-        const uint32_t t = lds[w];
-        if (w < wave) before += t;
-        all += t;
-    }
-    __syncthreads();
-    *total = all;
-    return before + incl - v;
-}
-
-__global__ __launch_bounds__(kScanBlock) void scan_totals_kernel(const uint32_t* __restrict__ x, int64_t n, uint32_t* __restrict__ totals) {
-    __shared__ uint32_t lds[kScanBlock / 64];
-    const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanPer;
-    uint32_t s = 0;
-#pragma unroll
-    for (int j = 0; j < kScanPer; j++)
-        if (base + j < n) s += x[base + j];
-    uint32_t total;
-    (void)block_exclusive_scan(s, lds, &total);
-    if (threadIdx.x == 0) totals[blockIdx.x] = total;
-}
-
-// offsets == nullptr: a single block scans the whole (short) array
-__global__ __launch_bounds__(kScanBlock) void scan_local_kernel(uint32_t* __restrict__ x, int64_t n, const uint32_t* __restrict__ offsets) {
-    __shared__ uint32_t lds[kScanBlock / 64];
-    const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanPer;
-    uint32_t v[kScanPer], s = 0;
-#pragma unroll
-    for (int j = 0; j < kScanPer; j++) {
-        v[j] = base + j < n ? x[base + j] : 0u;
-        s += v[j];
-    }
-    uint32_t total;
-    uint32_t run = block_exclusive_scan(s, lds, &total) + (offsets ? offsets[blockIdx.x] : 0u);
-#pragma unroll
-    for (int j = 0; j < kScanPer; j++) {
-        if (base + j < n) x[base + j] = run;
-        run += v[j];
-    }
-}
-
-// scratch: at least scan_scratch_words(n) uint32 behind the array's own storage
-size_t scan_scratch_words(int64_t n) {
-    size_t words = 0;
-    while (n > kScanTile) {
-        n = (n + kScanTile - 1) / kScanTile;
-        words += (size_t)n;
-    }
-    return words;
-}
-
-int exclusive_scan(skr_ctx* ctx, uint32_t* x, int64_t n, uint32_t* scratch) {
-    if (n <= kScanTile) {
-        hipLaunchKernelGGL(scan_local_kernel, dim3(1), dim3(kScanBlock), 0, ctx->stream, x, n, (const uint32_t*)nullptr);
-        SKR_HIP(hipGetLastError());
-        return SKR_OK;
-    }
-    const int64_t blocks = (n + kScanTile - 1) / kScanTile;
-    hipLaunchKernelGGL(scan_totals_kernel, dim3((unsigned)blocks), dim3(kScanBlock), 0, ctx->stream, x, n, scratch);
-    SKR_HIP(hipGetLastError());
-    SKR_TRY(exclusive_scan(ctx, scratch, blocks, scratch + blocks));
-    hipLaunchKernelGGL(scan_local_kernel, dim3((unsigned)blocks), dim3(kScanBlock), 0, ctx->stream, x, n, (const uint32_t*)scratch);
-    SKR_HIP(hipGetLastError());
-    return SKR_OK;
-}
+using skr_radix::exclusive_scan;
+using skr_radix::scan_scratch_words;
 
 int bit_length(uint64_t v) {
     int b = 0;
@@ -317,7 +226,7 @@ extern "C" int skr_pearson_gemm_edges(skr_ctx* ctx, const skr_operand* a, const 
         ra.vals_out = last ? (float*)out_vals->data : vbuf[cur ^ 1];
         hipLaunchKernelGGL(radix_count_kernel, dim3((unsigned)ra.n_chunks), dim3(64), 0, ctx->stream, ra);
         SKR_HIP(hipGetLastError());
-        SKR_TRY(exclusive_scan(ctx, ra.table, (int64_t)plan.table_words, scan_scratch));
+        SKR_TRY(exclusive_scan<uint32_t>(ctx, ra.table, (int64_t)plan.table_words, scan_scratch));
         if (last)
             hipLaunchKernelGGL(radix_scatter_kernel<true>, dim3((unsigned)ra.n_chunks), dim3(64), 0, ctx->stream, ra);
         else

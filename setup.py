@@ -15,6 +15,7 @@ setup(
             "seekr_kmer_counts = seekr_amd.console_scripts:console_kmer_counts",
             "seekr_pearson = seekr_amd.console_scripts:console_pearson",
             "seekr_norm_vectors = seekr_amd.console_scripts:console_norm_vectors",
+            "seekr_adj_pval = seekr_amd.console_scripts:console_adj_pval",
         ]
     },
 )
