@@ -4,7 +4,7 @@
 //   symmetric_kernel   is_symmetric's value test: each tile against its mirror tile (staged in LDS), diagonal skipped
 //   key_bits_kernel    AND / OR of the tests' order-preserving keys: a radix pass whose digit is the same in every key
 //                      (one bucket) is skipped
-//   key_count/scatter  key-only LSD radix sort, 8 bits per pass (radix.hpp), NaN last, -0.0 sorted as +0.0
+//   KeyPass            the key policy of radix.hpp's LSD radix sort: keys only, NaN last, -0.0 sorted as +0.0
 //   scan_*             the method's values in sorted order fused into a running max (or a running min from the end):
 //                      block aggregate -> scan of the block aggregates -> block fix-up; NaN wins as in numpy
 //   mapback_kernel     each test cell finds its value's first sorted position (two-level lower-bound search) and writes
@@ -24,7 +24,6 @@
 namespace {
 
 using skr_radix::kDigits;
-using skr_radix::same_digit;
 
 constexpr int64_t kHommelLimit = (int64_t)1 << 22;
 
@@ -102,55 +101,18 @@ __global__ __launch_bounds__(256) void key_bits_kernel(const K* __restrict__ in,
     }
 }
 
-struct SortArgs {
-    int64_t n, chunk, n_chunks;
+// the sort's policy (radix.hpp): keys only; the first pass (RAW) reads the float bits and turns them into keys
+template <typename K, bool RAW>
+struct KeyPass {
+    using Count = unsigned long long;  // up to 2.5e9 tests
+    using Item = K;
+    const K* in;
+    K* out;
     int shift;
-    unsigned long long* table;  // [256][n_chunks] counts, then (scanned in place) start offsets
+    __device__ __forceinline__ K load(int64_t i) const { return RAW ? key_of_bits<K>(in[i]) : in[i]; }
+    __device__ __forceinline__ uint32_t digit(K k) const { return (uint32_t)(k >> shift) & (kDigits - 1); }
+    __device__ __forceinline__ void store(unsigned long long pos, K k) const { out[pos] = k; }
 };
-
-template <typename K, bool RAW>
-__global__ __launch_bounds__(64) void key_count_kernel(const K* __restrict__ in, const SortArgs a) {
-    __shared__ uint32_t cnt[kDigits];
-    const int lane = threadIdx.x;
-    const int64_t c = blockIdx.x;
-    for (int d = lane; d < kDigits; d += 64) cnt[d] = 0;
-    __syncthreads();
-    const int64_t begin = c * a.chunk, end = std::min(a.n, begin + a.chunk);
-    for (int64_t i = begin + lane; i - lane < end; i += 64) {
-        const bool live = i < end;
-        const K k = live ? (RAW ? key_of_bits<K>(in[i]) : in[i]) : (K)0;
-        const uint32_t d = (uint32_t)(k >> a.shift) & (kDigits - 1);
-        const unsigned long long peers = same_digit(d, live);
-        if (live && (peers >> lane) == 1ull) cnt[d] += (uint32_t)__popcll(peers);
-        __syncthreads();
-    }
-    for (int d = lane; d < kDigits; d += 64) a.table[(size_t)d * a.n_chunks + c] = cnt[d];
-}
-
-template <typename K, bool RAW>
-__global__ __launch_bounds__(64) void key_scatter_kernel(const K* __restrict__ in, K* __restrict__ out, const SortArgs a) {
-    __shared__ unsigned long long base[kDigits];
-    const int lane = threadIdx.x;
-    const int64_t c = blockIdx.x;
-    for (int d = lane; d < kDigits; d += 64) base[d] = a.table[(size_t)d * a.n_chunks + c];
-    __syncthreads();
-    const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
-    const int64_t begin = c * a.chunk, end = std::min(a.n, begin + a.chunk);
-    for (int64_t i = begin + lane; i - lane < end; i += 64) {
-        const bool live = i < end;
-        const K k = live ? (RAW ? key_of_bits<K>(in[i]) : in[i]) : (K)0;
-        const uint32_t d = (uint32_t)(k >> a.shift) & (kDigits - 1);
-        const unsigned long long peers = same_digit(d, live);
-        unsigned long long pos = 0;
-        if (live) pos = base[d] + (unsigned long long)__popcll(peers & below);
-        __syncthreads();  // every lane has read its digit's running start before any group leader moves it
-        if (live) {
-            if ((peers >> lane) == 1ull) base[d] += (unsigned long long)__popcll(peers);
-            out[pos] = k;
-        }
-        __syncthreads();
-    }
-}
 
 // ------------------------------------------------------------------------------------- per-method values + scan --
 struct Raw {
@@ -465,12 +427,9 @@ __global__ __launch_bounds__(256) void hommel_cells_kernel(const typename KeyOf<
 }
 
 // ---------------------------------------------------------------------------------------------------- planning --
-unsigned grid_of(const skr_ctx* ctx, int64_t items) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + 255) / 256, (int64_t)ctx->num_cu * 8));
-}
-
 struct Plan {
-    int64_t n = 0, chunk = 0, n_chunks = 0, acc_blocks = 0;
+    int64_t n = 0, acc_blocks = 0;
+    skr_radix::Chunks sort;
     size_t off_keys_a = 0, off_keys_b = 0, off_c = 0, off_table = 0, off_scan = 0, off_acc = 0, off_hommel = 0,
            off_misc = 0, bytes = 0;
 };
@@ -480,13 +439,8 @@ size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 Plan plan_for(const skr_ctx* ctx, int64_t n, size_t key_bytes, bool hommel) {
     Plan p;
     p.n = n;
-    const int64_t want_waves = (int64_t)ctx->num_cu * 16;
-    int64_t chunk = (n + want_waves - 1) / want_waves;
-    chunk = std::min<int64_t>(8192, std::max<int64_t>(512, chunk));
-    p.chunk = (chunk + 63) / 64 * 64;
-    p.n_chunks = std::max<int64_t>(1, (n + p.chunk - 1) / p.chunk);
+    p.sort = skr_radix::plan_chunks(ctx, n);
     p.acc_blocks = std::max<int64_t>(1, (n + kAccTile - 1) / kAccTile);
-    const size_t table_words = (size_t)kDigits * (size_t)p.n_chunks;
     size_t off = 0;
     p.off_misc = off;
     off += 256;
@@ -497,9 +451,9 @@ Plan plan_for(const skr_ctx* ctx, int64_t n, size_t key_bytes, bool hommel) {
     p.off_c = off;
     off = align256(off + (size_t)n * 8);
     p.off_table = off;
-    off = align256(off + table_words * 8);
+    off = align256(off + p.sort.table_words * 8);
     p.off_scan = off;
-    off = align256(off + (skr_radix::scan_scratch_words((int64_t)table_words) + 16) * 8);
+    off = align256(off + (p.sort.scan_words + 16) * 8);
     p.off_acc = off;  // scan aggregates, or fdr_by's buffer sums
     off = align256(off + (size_t)std::max<int64_t>(p.acc_blocks, (n + 8191) / 8192 + 1) * 8);
     p.off_hommel = off;
@@ -527,7 +481,7 @@ int sort_keys(skr_ctx* ctx, const Plan& plan, char* base, const void* raw, const
     K* and_or = (K*)(base + 64);
     const K init[2] = {~(K)0, (K)0};
     SKR_HIP(hipMemcpyAsync(and_or, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL((key_bits_kernel<K, true>), dim3(grid_of(ctx, n)), dim3(256), 0, ctx->stream, (const K*)raw, n, and_or);
+    hipLaunchKernelGGL((key_bits_kernel<K, true>), dim3(skr_grid(ctx, n)), dim3(256), 0, ctx->stream, (const K*)raw, n, and_or);
     SKR_HIP(hipGetLastError());
     K host[2];
     SKR_HIP(hipMemcpyAsync(host, and_or, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
@@ -539,28 +493,16 @@ int sort_keys(skr_ctx* ctx, const Plan& plan, char* base, const void* raw, const
         if ((varying >> (8 * pss)) & 0xff) wanted[n_wanted++] = pss;
     if (n_wanted == 0) wanted[n_wanted++] = passes - 1;  // one value throughout: one pass still turns it into keys
     K* buf[2] = {(K*)(base + plan.off_keys_a), (K*)(base + plan.off_keys_b)};
-    SortArgs sa;
-    sa.n = n;
-    sa.chunk = plan.chunk;
-    sa.n_chunks = plan.n_chunks;
-    sa.table = (unsigned long long*)(base + plan.off_table);
+    unsigned long long* table = (unsigned long long*)(base + plan.off_table);
     unsigned long long* scan_scratch = (unsigned long long*)(base + plan.off_scan);
     const K* in = (const K*)raw;
     int cur = raw == (const void*)buf[0] ? 1 : 0;  // the output buffer of the first pass
     for (int w = 0; w < n_wanted; w++) {
-        sa.shift = 8 * wanted[w];
         K* out = buf[cur];
         if (w == 0)
-            hipLaunchKernelGGL((key_count_kernel<K, true>), dim3((unsigned)sa.n_chunks), dim3(64), 0, ctx->stream, in, sa);
+            SKR_TRY(skr_radix::run_pass(ctx, KeyPass<K, true>{in, out, 8 * wanted[w]}, n, plan.sort, table, scan_scratch));
         else
-            hipLaunchKernelGGL((key_count_kernel<K, false>), dim3((unsigned)sa.n_chunks), dim3(64), 0, ctx->stream, in, sa);
-        SKR_HIP(hipGetLastError());
-        SKR_TRY(skr_radix::exclusive_scan<unsigned long long>(ctx, sa.table, (int64_t)kDigits * sa.n_chunks, scan_scratch));
-        if (w == 0)
-            hipLaunchKernelGGL((key_scatter_kernel<K, true>), dim3((unsigned)sa.n_chunks), dim3(64), 0, ctx->stream, in, out, sa);
-        else
-            hipLaunchKernelGGL((key_scatter_kernel<K, false>), dim3((unsigned)sa.n_chunks), dim3(64), 0, ctx->stream, in, out, sa);
-        SKR_HIP(hipGetLastError());
+            SKR_TRY(skr_radix::run_pass(ctx, KeyPass<K, false>{in, out, 8 * wanted[w]}, n, plan.sort, table, scan_scratch));
         in = out;
         cur ^= 1;
     }
@@ -606,13 +548,13 @@ int adjust_typed(skr_ctx* ctx, const skr_mat* p, int method, double alpha, bool 
         SkrProfScope prof(ctx, "adjust_elementwise");
         const int sidak = method == SKR_ADJ_SIDAK;
         if (upper)
-            hipLaunchKernelGGL((elementwise_kernel<T, double, true>), dim3(grid_of(ctx, cells)), dim3(256), 0, ctx->stream, pd,
+            hipLaunchKernelGGL((elementwise_kernel<T, double, true>), dim3(skr_grid(ctx, cells)), dim3(256), 0, ctx->stream, pd,
                                cols, cells, n, sidak, (double*)out->data);
         else if (out_dtype == SKR_F64)
-            hipLaunchKernelGGL((elementwise_kernel<T, double, false>), dim3(grid_of(ctx, cells)), dim3(256), 0, ctx->stream, pd,
+            hipLaunchKernelGGL((elementwise_kernel<T, double, false>), dim3(skr_grid(ctx, cells)), dim3(256), 0, ctx->stream, pd,
                                cols, cells, n, sidak, (double*)out->data);
         else
-            hipLaunchKernelGGL((elementwise_kernel<T, T, false>), dim3(grid_of(ctx, cells)), dim3(256), 0, ctx->stream, pd,
+            hipLaunchKernelGGL((elementwise_kernel<T, T, false>), dim3(skr_grid(ctx, cells)), dim3(256), 0, ctx->stream, pd,
                                cols, cells, n, sidak, (T*)out->data);
         SKR_HIP(hipGetLastError());
         return SKR_OK;
@@ -689,7 +631,8 @@ int adjust_typed(skr_ctx* ctx, const skr_mat* p, int method, double alpha, bool 
                 const double alpha_prime = bky ? alpha / fact : alpha;
                 unsigned long long* r1d = (unsigned long long*)(base + 128);
                 SKR_HIP(hipMemsetAsync(r1d, 0, 8, ctx->stream));
-                hipLaunchKernelGGL(rejections_kernel<T>, dim3(grid_of(ctx, n)), dim3(256), 0, ctx->stream, sorted, n, alpha_prime, r1d);
+                hipLaunchKernelGGL(rejections_kernel<T>, dim3(skr_grid(ctx, n)), dim3(256), 0, ctx->stream, sorted, n, alpha_prime,
+                                   r1d);
                 SKR_HIP(hipGetLastError());
                 unsigned long long r1 = 0;
                 SKR_HIP(hipMemcpyAsync(&r1, r1d, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -704,7 +647,7 @@ int adjust_typed(skr_ctx* ctx, const skr_mat* p, int method, double alpha, bool 
         }
     }
     SkrProfScope prof(ctx, "adjust_mapback");
-    const dim3 grid(grid_of(ctx, cells));
+    const dim3 grid(skr_grid(ctx, cells));
     if (upper)
         hipLaunchKernelGGL((mapback_kernel<T, double, true>), grid, dim3(256), 0, ctx->stream, pd, cols, cells, sorted, n, c, fin,
                            (double*)out->data);

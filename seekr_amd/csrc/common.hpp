@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -183,6 +184,11 @@ int skr_launch_gemm_split(skr_ctx* ctx, int precision, const void* As, const voi
 // contraction and for every caller that must know whether a launch will have more than one k chunk (fused_edges.hip).
 inline int64_t skr_gemm_chunk_tiles(const skr_ctx* ctx, bool coherent) {
     return ctx->knobs.gemm_chunk_tiles ? ctx->knobs.gemm_chunk_tiles : (coherent ? 32 : 128);
+}
+
+// grid of a grid-stride kernel with 256-thread workgroups: one thread per item, at most 8 workgroups per CU
+inline unsigned skr_grid(const skr_ctx* ctx, int64_t items) {
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + 255) / 256, (int64_t)ctx->num_cu * 8));
 }
 
 // Where the EDGES mode of the split contraction appends the cells that survive a threshold (pearson_bf16.hip).

@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "radix.hpp"
 
 namespace {
 
@@ -108,33 +109,6 @@ __global__ __launch_bounds__(256) void edges_count_kernel(EdgeArgs a, unsigned l
         __syncthreads();
         if (threadIdx.x == 0) counts[i] = (unsigned long long)red[0] + red[1] + red[2] + red[3];
         __syncthreads();
-    }
-}
-
-// exclusive prefix sum of the per-row counts, in place; one workgroup (rows <= a few 10^5 per call)
-__global__ __launch_bounds__(1024) void edges_scan_kernel(unsigned long long* __restrict__ counts, int64_t n,
-                                                          unsigned long long* __restrict__ total) {
-    __shared__ unsigned long long part[1024];
-    const int64_t per = (n + 1023) / 1024, lo = std::min<int64_t>(n, threadIdx.x * per), hi = std::min<int64_t>(n, lo + per);
-    unsigned long long s = 0;
-    for (int64_t i = lo; i < hi; i++) s += counts[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long run = 0;
-        for (int t = 0; t < 1024; t++) {
-            const unsigned long long v = part[t];
-            part[t] = run;
-            run += v;
-        }
-        *total = run;
-    }
-    __syncthreads();
-    unsigned long long run = part[threadIdx.x];
-    for (int64_t i = lo; i < hi; i++) {
-        const unsigned long long v = counts[i];
-        counts[i] = run;
-        run += v;
     }
 }
 
@@ -242,11 +216,6 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
     }
 }
 
-unsigned grid_for(const skr_ctx* ctx, int64_t items) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + 255) / 256, (int64_t)ctx->num_cu * 8));
-}
-
-
 // ---------------------------------------------------------------------------------------
 // Parametric p-values (find_pval.py:118-133): p[i,j] = 1 - dist(*params).cdf(sim[i,j]) for the scipy.stats
 // distribution find_dist fitted (find_dist.py:96-98, the `common10` list).  scipy evaluates the cdf of a float32
@@ -325,7 +294,7 @@ extern "C" int skr_threshold_zero_diag(skr_ctx* ctx, skr_mat* r, float cutoff, i
     SKR_TRY(skr_activate(ctx));
     if (r->rows * r->cols == 0) return SKR_OK;
     SkrProfScope prof(ctx, "threshold_zero_diag");
-    hipLaunchKernelGGL(threshold_zero_diag_kernel, dim3(grid_for(ctx, r->rows * r->cols)), dim3(256), 0, ctx->stream,
+    hipLaunchKernelGGL(threshold_zero_diag_kernel, dim3(skr_grid(ctx, r->rows * r->cols)), dim3(256), 0, ctx->stream,
                        (float*)r->data, r->rows, r->cols, cutoff, diag_col0);
     SKR_HIP(hipGetLastError());
     return SKR_OK;
@@ -366,7 +335,7 @@ extern "C" int skr_gather_f32(skr_ctx* ctx, const skr_mat* src, const int64_t* i
     int64_t* d_idx = (int64_t*)ws;
     float* d_out = (float*)((char*)ws + (size_t)n * 8);
     SKR_HIP(hipMemcpyAsync(d_idx, idx_host, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(gather_kernel, dim3(grid_for(ctx, n)), dim3(256), 0, ctx->stream, (const float*)src->data, d_idx, n,
+    hipLaunchKernelGGL(gather_kernel, dim3(skr_grid(ctx, n)), dim3(256), 0, ctx->stream, (const float*)src->data, d_idx, n,
                        d_out);
     SKR_HIP(hipGetLastError());
     SKR_HIP(hipMemcpyAsync(out_host, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -385,7 +354,7 @@ extern "C" int skr_empirical_pvalues(skr_ctx* ctx, const skr_mat* r, const skr_m
     const int64_t cells = r->rows * r->cols;
     if (cells == 0) return SKR_OK;
     SkrProfScope prof(ctx, "empirical_pvalues");
-    hipLaunchKernelGGL(empirical_p_kernel, dim3(grid_for(ctx, cells)), dim3(256), 0, ctx->stream, (const float*)r->data,
+    hipLaunchKernelGGL(empirical_p_kernel, dim3(skr_grid(ctx, cells)), dim3(256), 0, ctx->stream, (const float*)r->data,
                        cells, (const float*)sorted_bg->data, sorted_bg->rows * sorted_bg->cols, (double)total_len,
                        (float*)p->data);
     SKR_HIP(hipGetLastError());
@@ -411,9 +380,11 @@ extern "C" int skr_edges(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t 
     *count = 0;
     if (nrows == 0 || col_begin == col_end) return SKR_OK;
     void* ws = nullptr;
-    SKR_TRY(skr_ctx_workspace(ctx, (size_t)(nrows + 2) * 8, &ws));
+    // per-row counts and a zero behind them: scanned in place, offsets[nrows] is the total.  Then the scan's scratch.
+    SKR_TRY(skr_ctx_workspace(ctx, ((size_t)nrows + 1 + skr_radix::scan_scratch_words(nrows + 1)) * 8, &ws));
     unsigned long long* counts = (unsigned long long*)ws;
     unsigned long long* total = counts + nrows;
+    SKR_HIP(hipMemsetAsync(total, 0, 8, ctx->stream));
     EdgeArgs a{(const float*)r->data, r->cols, nrows, col_begin, col_end, row_global0, col_global0, cutoff, upper_only != 0};
     const unsigned grid = (unsigned)std::min<int64_t>(nrows, (int64_t)ctx->num_cu * 16);
     {
@@ -421,8 +392,7 @@ extern "C" int skr_edges(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t 
         hipLaunchKernelGGL(edges_count_kernel, dim3(grid), dim3(256), 0, ctx->stream, a, counts);
         SKR_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(edges_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, counts, nrows, total);
-    SKR_HIP(hipGetLastError());
+    SKR_TRY(skr_radix::exclusive_scan<unsigned long long>(ctx, counts, nrows + 1, total + 1));
     unsigned long long h_total = 0;
     SKR_HIP(hipMemcpyAsync(&h_total, total, 8, hipMemcpyDeviceToHost, ctx->stream));
     SKR_HIP(hipStreamSynchronize(ctx->stream));
@@ -489,7 +459,7 @@ extern "C" int skr_parametric_pvalues(skr_ctx* ctx, const skr_mat* r, const char
     const int64_t cells = r->rows * r->cols;
     if (cells == 0) return SKR_OK;
     SkrProfScope prof(ctx, "parametric_pvalues");
-    hipLaunchKernelGGL(parametric_p_kernel, dim3(grid_for(ctx, cells)), dim3(256), 0, ctx->stream, (const float*)r->data, cells, d,
+    hipLaunchKernelGGL(parametric_p_kernel, dim3(skr_grid(ctx, cells)), dim3(256), 0, ctx->stream, (const float*)r->data, cells, d,
                        (float*)p->data);
     SKR_HIP(hipGetLastError());
     return SKR_OK;

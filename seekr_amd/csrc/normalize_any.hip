@@ -402,8 +402,7 @@ extern "C" int skr_host_apply(skr_ctx* ctx, void* x, int64_t rows, int64_t cols,
     SKR_HIP(hipMemsetAsync(ctx->d_flags + 1, 0, 4, ctx->stream));
     {
         SkrProfScope prof(ctx, "elementwise_any");
-        const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, (int64_t)ctx->num_cu * 8));
-        hipLaunchKernelGGL(elementwise_any_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, dx.p, rows, cols, np_type, op,
+        hipLaunchKernelGGL(elementwise_any_kernel, dim3(skr_grid(ctx, total)), dim3(256), 0, ctx->stream, dx.p, rows, cols, np_type, op,
                            (const void*)dv.p, vec_is_f64, dy.p, y_np_type, ctx->d_flags);
     }
     SKR_HIP(hipGetLastError());

@@ -86,7 +86,8 @@ def nonzero_edges(r, cutoff, upper):
     return i.astype(np.uint32), j.astype(np.uint32), want[i, j]
 
 
-@pytest.mark.parametrize("n,m,cutoff", [(301, 301, 0.1), (64, 1000, 0.25), (513, 513, -5.0), (100, 100, 2.0), (257, 255, 0.0)])
+@pytest.mark.parametrize("n,m,cutoff", [(301, 301, 0.1), (64, 1000, 0.25), (513, 513, -5.0), (100, 100, 2.0), (257, 255, 0.0),
+                                        (4500, 130, 0.1)])
 def test_edges_of_a_block_match_numpy(n, m, cutoff, ctx):
     from seekr_amd import consumers
     r = rand_r(n, m, seed=n)
