@@ -382,7 +382,10 @@ int skr_empirical_pvalues(skr_ctx* ctx, const skr_mat* r, const skr_mat* sorted_
 /* p[i,j] = float32(1 - dist(*params).cdf(r[i,j])), find_pval.py:118-133 with the scipy.stats distribution that
  * find_dist fitted: dist_name one of cauchy, chi2, expon, exponpow, gamma, lognorm, norm, pareto, rayleigh,
  * uniform (find_dist.py:96-98); params = shape parameter (where the distribution has one), loc, scale — the
- * tuple find_dist returns.  Evaluated in float64 like scipy; other names: SKR_ERR_UNSUPPORTED.                */
+ * tuple find_dist returns.  Evaluated in float64 like scipy; other names: SKR_ERR_UNSUPPORTED.  A shape parameter
+ * that is zero, negative or NaN gives scipy's all-NaN matrix.  gamma and chi2 cover gamma shapes (chi2: df / 2)
+ * from 1e-6 to 1e7: outside that range, or if the incomplete gamma function does not converge within its term
+ * bound for some cell, SKR_ERR_UNSUPPORTED (p then holds no valid result).                                      */
 int skr_parametric_pvalues(skr_ctx* ctx, const skr_mat* r, const char* dist_name, const double* params, int n_params,
                            skr_mat* p);
 

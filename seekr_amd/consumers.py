@@ -47,9 +47,22 @@ def subsample(values, size, rng=None):
     return out
 
 
+def ceil_float32(values):
+    """The smallest float32 >= each value (NaN stays NaN).  The reference compares `fitres > sim[i, j]` in the
+    background's own precision.  For a float32 v, b > v exactly when ceil32(b) > v: no float32 lies strictly between b and
+    ceil32(b), so v < b implies v < ceil32(b) or v = ceil32(b) = b, and ceil32(b) >= b gives the converse.  Rounding to
+    nearest instead moves a value that sits just above a cell onto or below it, and the count is one short."""
+    wide = np.asarray(values, dtype=np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        near = wide.astype(np.float32)  # beyond float32's range: +-inf, and -inf steps up to -FLT_MAX below
+        return np.where(near < wide, np.nextafter(near, np.float32(np.inf)), near).astype(np.float32)
+
+
 def empirical_pvalues(r, fitres):
     """Device matrix of p-values for the device matrix `r` against the 1-D background `fitres`."""
-    fitres = np.asarray(fitres, dtype=np.float32).reshape(-1)
+    fitres = np.asarray(fitres).reshape(-1)
+    if fitres.dtype != np.float32:
+        fitres = ceil_float32(fitres)
     bg = np.sort(fitres[~np.isnan(fitres)])
     ctx = r.ctx
     if len(bg) == 0:  # nothing compares greater: every count is 0

@@ -223,27 +223,44 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
 // kernel does the same, one cell per thread.  params = shape parameters..., loc, scale as scipy orders them.
 // ---------------------------------------------------------------------------------------
 enum { DIST_CAUCHY = 0, DIST_CHI2, DIST_EXPON, DIST_EXPONPOW, DIST_GAMMA, DIST_LOGNORM, DIST_NORM, DIST_PARETO, DIST_RAYLEIGH,
-       DIST_UNIFORM, DIST_COUNT };
+       DIST_UNIFORM, DIST_COUNT, DIST_BAD_SHAPE };
 
 // regularised lower incomplete gamma P(a, x), float64: series for x < a + 1, Lentz continued fraction for Q otherwise
-// (Abramowitz & Stegun 6.5.29 / 6.5.31; both converge to ~1e-16 within a few hundred terms for the shapes a fit returns)
-__device__ double gamma_p(double a, double x) {
+// (Abramowitz & Stegun 6.5.29 / 6.5.31).  Near x = a the terms of both fall like exp(-n^2 / 2a): reaching 1e-17 takes
+// about 8.2 sqrt(a) of them at every shape from 1e2 to 1e8, and at most 110 for shapes below 50 (the fraction just
+// above x = a + 1 for a small shape) — counted in a float64 port of these loops.  A fit to Pearson similarities does
+// return shapes of 1e5 and more (a gamma that imitates a normal), so the loops run up to
+//     gamma_max_terms(a) = 200 + 12 sqrt(a)      (38 147 at kGammaMaxShape)
+// terms, 1.4 times what was counted.  Shapes outside [kGammaMinShape, kGammaMaxShape] are refused on the host: above,
+// the rounding of a log(x) - lgamma(a) in the prefactor grows with a (against scipy the port uses 0.06 of the tests'
+// 2e-6 relative bar at a = 1e7 and 0.43 at 1e8) and nothing is tested; below, 1 - P loses its digits (past the bar at
+// a = 1e-10).  A loop that ends without converging sets `failed`: the call then fails instead of returning a number
+// that is not scipy's.
+constexpr double kGammaMinShape = 1e-6, kGammaMaxShape = 1e7;
+inline int gamma_max_terms(double a) { return 200 + (int)(12.0 * sqrt(a)); }
+
+__device__ double gamma_p(double a, double x, int max_terms, bool& failed) {
     if (!(x > 0.0)) return 0.0;
     if (isinf(x)) return 1.0;
     const double lg = lgamma(a);
+    bool converged = false;
     if (x < a + 1.0) {
         double ap = a, del = 1.0 / a, sum = del;
-        for (int n = 0; n < 2000; n++) {
+        for (int n = 0; n < max_terms; n++) {  // bounded: max_terms <= gamma_max_terms(kGammaMaxShape)
             ap += 1.0;
             del *= x / ap;
             sum += del;
-            if (fabs(del) < fabs(sum) * 1e-17) break;
+            if (fabs(del) < fabs(sum) * 1e-17) {
+                converged = true;
+                break;
+            }
         }
+        if (!converged) failed = true;
         return sum * exp(-x + a * log(x) - lg);
     }
     const double tiny = 1e-300;
     double b = x + 1.0 - a, c = 1.0 / tiny, d = 1.0 / b, h = d;
-    for (int i = 1; i < 2000; i++) {
+    for (int i = 1; i <= max_terms; i++) {  // bounded likewise
         const double an = -(double)i * ((double)i - a);
         b += 2.0;
         d = an * d + b;
@@ -253,24 +270,30 @@ __device__ double gamma_p(double a, double x) {
         d = 1.0 / d;
         const double del = d * c;
         h *= del;
-        if (fabs(del - 1.0) < 1e-16) break;
+        if (fabs(del - 1.0) < 1e-16) {
+            converged = true;
+            break;
+        }
     }
+    if (!converged) failed = true;
     return 1.0 - exp(-x + a * log(x) - lg) * h;
 }
 
 struct DistParams {
     int dist;
     double shape, loc, scale;
+    int max_terms;        // of gamma_p's loops (gamma, chi2)
+    int* not_converged;   // device flag a cell raises when such a loop ends unconverged (gamma, chi2; else NULL)
 };
 
-__device__ __forceinline__ double dist_cdf(const DistParams& d, double x) {
+__device__ __forceinline__ double dist_cdf(const DistParams& d, double x, bool& failed) {
     const double z = (x - d.loc) / d.scale;
     switch (d.dist) {
         case DIST_CAUCHY: return 0.5 + atan(z) / 3.14159265358979323846;
-        case DIST_CHI2: return z > 0.0 ? gamma_p(0.5 * d.shape, 0.5 * z) : 0.0;
+        case DIST_CHI2: return z > 0.0 ? gamma_p(0.5 * d.shape, 0.5 * z, d.max_terms, failed) : 0.0;
         case DIST_EXPON: return z > 0.0 ? -expm1(-z) : 0.0;
         case DIST_EXPONPOW: return z > 0.0 ? -expm1(-expm1(pow(z, d.shape))) : 0.0;
-        case DIST_GAMMA: return z > 0.0 ? gamma_p(d.shape, z) : 0.0;
+        case DIST_GAMMA: return z > 0.0 ? gamma_p(d.shape, z, d.max_terms, failed) : 0.0;
         case DIST_LOGNORM: return z > 0.0 ? 0.5 * erfc(-(log(z) / d.shape) * 0.70710678118654752440) : 0.0;
         case DIST_NORM: return 0.5 * erfc(-z * 0.70710678118654752440);
         case DIST_PARETO: return z >= 1.0 ? 1.0 - pow(z, -d.shape) : 0.0;
@@ -281,10 +304,13 @@ __device__ __forceinline__ double dist_cdf(const DistParams& d, double x) {
 
 __global__ __launch_bounds__(256) void parametric_p_kernel(const float* __restrict__ r, int64_t cells, DistParams d,
                                                            float* __restrict__ p) {
+    bool failed = false;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cells; i += (int64_t)gridDim.x * blockDim.x) {
         const double x = (double)r[i];
-        p[i] = x != x ? NAN : (float)(1.0 - dist_cdf(d, x));  // cdf(nan) is nan in scipy
+        // cdf(nan) is nan in scipy; so is every cdf of a distribution whose shape parameter fails scipy's _argcheck
+        p[i] = (x != x || d.dist == DIST_BAD_SHAPE) ? NAN : (float)(1.0 - dist_cdf(d, x, failed));
     }
+    if (failed && d.not_converged) atomicOr(d.not_converged, 1);  // gamma / chi2 only: the others never set it
 }
 
 }  // namespace
@@ -439,7 +465,7 @@ extern "C" int skr_parametric_pvalues(skr_ctx* ctx, const skr_mat* r, const char
         {"cauchy", DIST_CAUCHY, 0}, {"chi2", DIST_CHI2, 1}, {"expon", DIST_EXPON, 0}, {"exponpow", DIST_EXPONPOW, 1},
         {"gamma", DIST_GAMMA, 1}, {"lognorm", DIST_LOGNORM, 1}, {"norm", DIST_NORM, 0}, {"pareto", DIST_PARETO, 1},
         {"rayleigh", DIST_RAYLEIGH, 0}, {"uniform", DIST_UNIFORM, 0}};
-    DistParams d{-1, 0.0, 0.0, 1.0};
+    DistParams d{-1, 0.0, 0.0, 1.0, 0, nullptr};
     for (const auto& k : kDists) {
         if (strcmp(k.name, dist_name) != 0) continue;
         // scipy: dist(*shapes, loc=0, scale=1); find_dist's fit returns all of them
@@ -455,12 +481,42 @@ extern "C" int skr_parametric_pvalues(skr_ctx* ctx, const skr_mat* r, const char
                              "distribution '%s' has no device cdf (available: cauchy, chi2, expon, exponpow, gamma, lognorm, "
                              "norm, pareto, rayleigh, uniform — find_dist's common10 list)", dist_name);
     SKR_REQUIRE(d.scale > 0.0, "scale must be positive");
+    const bool has_shape = d.dist == DIST_CHI2 || d.dist == DIST_EXPONPOW || d.dist == DIST_GAMMA || d.dist == DIST_LOGNORM ||
+                           d.dist == DIST_PARETO;
+    const bool is_gamma = d.dist == DIST_CHI2 || d.dist == DIST_GAMMA;
+    if (has_shape && !(d.shape > 0.0)) {
+        d.dist = DIST_BAD_SHAPE;  // zero, negative or NaN: scipy's _argcheck fails and every cell is NaN
+    } else if (is_gamma) {
+        const double a = d.dist == DIST_CHI2 ? 0.5 * d.shape : d.shape;
+        if (!(a >= kGammaMinShape && a <= kGammaMaxShape))
+            return skr_set_error(SKR_ERR_UNSUPPORTED,
+                                 "%s with shape %g: the device's incomplete gamma function covers gamma shapes (chi2: df / 2) "
+                                 "from %g to %g", dist_name, d.shape, kGammaMinShape, kGammaMaxShape);
+        d.max_terms = gamma_max_terms(a);
+    }
     SKR_TRY(skr_activate(ctx));
     const int64_t cells = r->rows * r->cols;
     if (cells == 0) return SKR_OK;
-    SkrProfScope prof(ctx, "parametric_pvalues");
-    hipLaunchKernelGGL(parametric_p_kernel, dim3(skr_grid(ctx, cells)), dim3(256), 0, ctx->stream, (const float*)r->data, cells, d,
-                       (float*)p->data);
-    SKR_HIP(hipGetLastError());
+    if (d.dist == DIST_CHI2 || d.dist == DIST_GAMMA) {
+        void* ws = nullptr;
+        SKR_TRY(skr_ctx_workspace(ctx, 64, &ws));
+        d.not_converged = (int*)ws;
+        SKR_HIP(hipMemsetAsync(d.not_converged, 0, sizeof(int), ctx->stream));
+    }
+    {
+        SkrProfScope prof(ctx, "parametric_pvalues");
+        hipLaunchKernelGGL(parametric_p_kernel, dim3(skr_grid(ctx, cells)), dim3(256), 0, ctx->stream, (const float*)r->data,
+                           cells, d, (float*)p->data);
+        SKR_HIP(hipGetLastError());
+    }
+    if (d.not_converged) {
+        int h_flag = 0;
+        SKR_HIP(hipMemcpyAsync(&h_flag, d.not_converged, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        SKR_HIP(hipStreamSynchronize(ctx->stream));
+        if (h_flag)
+            return skr_set_error(SKR_ERR_UNSUPPORTED,
+                                 "%s with shape %g: the incomplete gamma function did not converge within %d terms for some "
+                                 "cell; p holds no valid result", dist_name, d.shape, d.max_terms);
+    }
     return SKR_OK;
 }
