@@ -168,6 +168,21 @@ int skr_count_u32(skr_ctx* ctx, const skr_seqs* s, int k, skr_mat* out);
  * Returns SKR_ERR_ZERODIV if any sequence has length k-1.                                   */
 int skr_count_per_kb(skr_ctx* ctx, const skr_seqs* s, int k, int log2_pre, skr_mat* out);
 
+/* Sliding windows (no counterpart in the reference: the equivalence below is the specification).  Sequence i of `s`
+ * gives ceil(max(L_i - window, 0) / slide) + 1 windows; window j starts at base j * slide and is
+ * seq[start : start + window] as Python slices it (the last one may be shorter, a sequence shorter than `window` is one
+ * window); rows are ordered by sequence, then by start.  Row r of that table equals, bit for bit, the row
+ * skr_count_u32 / skr_count_per_kb give when the window's substring is packed as a sequence of its own — no substring is
+ * ever made: every window is counted from the packed sequence at its base offset.  first_row / n_rows select a run of
+ * rows of the table (a caller with a bounded output works in chunks; the table itself is kept with `s` from one call
+ * to the next); out is [n_rows, 4^k], SKR_U32 (skr_count_windows_u32) or SKR_F32 (skr_count_windows_per_kb; log2_pre as
+ * in skr_count_per_kb).  k <= 7; k >= 8 and SKR_F64 rows: SKR_ERR_UNSUPPORTED.  window < 1, slide < 1, slide > window:
+ * SKR_ERR_INVALID.  skr_count_windows_per_kb returns SKR_ERR_ZERODIV if a selected window holds exactly k-1 letters.   */
+int skr_count_windows_u32(skr_ctx* ctx, const skr_seqs* s, int k, int64_t window, int64_t slide, int64_t first_row,
+                          int64_t n_rows, skr_mat* out);
+int skr_count_windows_per_kb(skr_ctx* ctx, const skr_seqs* s, int k, int64_t window, int64_t slide, int64_t first_row,
+                             int64_t n_rows, int log2_pre, skr_mat* out);
+
 /* Any alphabet (kmer_counts.py:120-122 takes any string): `alen` letters give alen^k columns,
  * column = sum code(c_p) * alen^(k-1-p), code = position in `alphabet` — the LAST position for a
  * repeated letter, as the reference's dict {kmer: index} resolves it.  Sequences come as one ASCII

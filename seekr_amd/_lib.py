@@ -74,6 +74,8 @@ SIGNATURES = {
     "skr_seqs_headers": (_int, [_p, C.c_char_p, _i64, C.POINTER(_i64)]),
     "skr_count_u32": (_int, [_p, _p, _int, _p]),
     "skr_count_per_kb": (_int, [_p, _p, _int, _int, _p]),
+    "skr_count_windows_u32": (_int, [_p, _p, _int, _i64, _i64, _i64, _i64, _p]),
+    "skr_count_windows_per_kb": (_int, [_p, _p, _int, _i64, _i64, _i64, _i64, _int, _p]),
     "skr_colsum_seq": (_int, [_p, _p, _p, _p, _int, _p]),
     "skr_colsum_seq_colmin": (_int, [_p, _p, _p, _p]),
     "skr_chain_create": (_int, [_p, _i64, C.POINTER(_p)]),
@@ -850,6 +852,19 @@ def count_per_kb(ctx, seqs, k, log2_pre=False, dtype=np.float32, out=None):
     if out is None:
         out = ctx.empty(seqs.n, 4 ** k, dtype)
     check(lib().skr_count_per_kb(ctx._h, seqs._h, int(k), 1 if log2_pre else 0, out._h))
+    return out
+
+
+def count_windows(ctx, seqs, k, window, slide, first_row, n_rows, dtype=np.float32, log2_pre=False, out=None):
+    """Rows [first_row, first_row + n_rows) of the window table of the packed sequences (skr_count_windows_*): per-kb
+    float32 values, or raw uint32 counts; `out`: an existing [n_rows, 4^k] matrix to fill."""
+    out = ctx.empty(n_rows, 4 ** k, dtype) if out is None else out
+    dtype = out.dtype
+    if dtype == np.uint32:
+        check(lib().skr_count_windows_u32(ctx._h, seqs._h, int(k), int(window), int(slide), int(first_row), int(n_rows), out._h))
+    else:
+        check(lib().skr_count_windows_per_kb(ctx._h, seqs._h, int(k), int(window), int(slide), int(first_row), int(n_rows),
+                                             1 if log2_pre else 0, out._h))
     return out
 
 

@@ -1,5 +1,6 @@
 """`seekr_kmer_counts`, `seekr_pearson`, `seekr_norm_vectors` and `seekr_adj_pval` with the reference's flags
-(console_scripts.py:564-681, 887-918).  Only the commands on the hot path are provided."""
+(console_scripts.py:564-681, 887-918), and `seekr_domain_pearson` (sliding windows of a target against queries: no
+counterpart in the reference).  Only the commands on the hot path are provided."""
 import argparse
 import sys
 
@@ -60,6 +61,20 @@ Examples
 --------
     defaults (6-mers, mean.npy, std.npy):   seekr_norm_vectors gencode.fa
     5-mers, named outputs:                  seekr_norm_vectors gencode.fa -k 5 -mv mean5.npy -sv std5.npy
+"""
+
+DOMAIN_PEARSON_DOC = """
+Description
+-----------
+Pearson correlation between the k-mer profile of every query sequence and the profile of every sliding window of the
+target sequences, computed on an MI355X: which part of a long transcript or region resembles a query.  The windows are
+counted from the packed target on the device; both sides are normalised with the stored mean and std vectors
+(seekr_norm_vectors).  Rows of the output are the queries, columns the windows, labelled header:start-end.
+
+Examples
+--------
+    labelled CSV:   seekr_domain_pearson repeats.fa chrX_region.fa mean.npy std.npy -k 6 -w 1000 -s 100 -o r.csv
+    .npy:           seekr_domain_pearson repeats.fa chrX_region.fa mean.npy std.npy -w 500 -s 50 -o r.npy -bo
 """
 
 _LOG2 = ["Log2.post", "Log2.pre", "Log2.none"]
@@ -187,3 +202,31 @@ def console_adj_pval():
     args = _parse_args_or_exit(parser)
     pvals = _read_pval_csv(args.pval_path)
     adj_pval.adj_pval(pvals, args.method, float(args.alpha), args.outputname)
+
+
+def _run_domain_pearson(query, target, mean, std, kmer, window, slide, log2, outfile, binary_output):
+    from seekr_amd import windows
+    from seekr_amd.fasta_reader import Reader
+    r, table = windows.domain_pearson(query, target, kmer, window, slide, mean, std, log2=log2)
+    if binary_output:
+        _lib.save_npy(outfile, r)
+    else:
+        _lib.save_csv_labelled(outfile, r, Reader(query).get_headers(), windows.window_labels(table))
+
+
+def console_domain_pearson():
+    parser = argparse.ArgumentParser(usage=DOMAIN_PEARSON_DOC, formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    parser.add_argument("query", help="FASTA file with the query sequences (rows of the result).")
+    parser.add_argument("target", help="FASTA file with the target sequences; their sliding windows are the columns.")
+    parser.add_argument("mean", help="Stored mean vector (.npy) both sides are centred with.")
+    parser.add_argument("std", help="Stored std vector (.npy) both sides are scaled with.")
+    parser.add_argument("-k", "--kmer", default=6, help="k, the word length (4^k columns; up to 7).")
+    parser.add_argument("-w", "--window", default=1000, help="Letters per window.")
+    parser.add_argument("-s", "--slide", default=100, help="Letters between the starts of two windows (at most the window).")
+    parser.add_argument("-l", "--log2", default="Log2.post", choices=_LOG2,
+                        help="log2 before the column statistics (pre), after them (post), or not at all (none).")
+    parser.add_argument("-o", "--outfile", default="domain_pearson.seekr", help="Where the correlation matrix goes.")
+    parser.add_argument("-bo", "--binary_output", action="store_true", help="Write .npy instead of a labelled CSV.")
+    args = _parse_args_or_exit(parser)
+    _run_domain_pearson(args.query, args.target, args.mean, args.std, int(args.kmer), int(args.window), int(args.slide),
+                        args.log2, args.outfile, args.binary_output)

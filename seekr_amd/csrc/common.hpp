@@ -130,6 +130,11 @@ struct skr_seqs {
     int64_t* d_mask_off = nullptr;  // [n], -1 when the sequence is all-alphabet
     std::vector<int64_t> h_len;
     std::string headers;  // '\n' joined (FASTA input only)
+    // the window table of the last (window, slide) asked for (windows.hip): row_begin[i] = first row of sequence i,
+    // row_begin[n] = rows in all.  Built and uploaded once per (window, slide), not per chunk of rows.
+    mutable int64_t win_window = 0, win_slide = 0;
+    mutable std::vector<int64_t> h_row_begin;
+    mutable int64_t* d_row_begin = nullptr;  // [n+1]
 };
 
 int skr_set_error(int code, const char* fmt, ...);

@@ -38,32 +38,11 @@
 #include <vector>
 
 #include "common.hpp"
+#include "per_kb.hpp"  // kTabSize, per_kb_value, per_kb_value_f64, lds_add_u32
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kTabSize = 16;  // counts below this are looked up per sequence instead of recomputed
-
-// float32( n sequential float64 additions of `inc` ) — what kmer_counts.py:144-150 stores.
-// n*inc (one rounding) equals the sequential sum unless the product sits within the
-// accumulated rounding slack of a float32 rounding boundary; only then replay the additions.
-__device__ __forceinline__ float per_kb_value(uint32_t n, double inc) {
-    if (n == 0) return 0.0f;
-    const double p = (double)n * inc;
-    const float f = (float)p;
-    if (n <= 3) return f;  // 1*inc, inc+inc and fl(2inc+inc) are single roundings of n*inc
-    const double slack = p * ((double)(n + 4) * 0x1.0p-53);
-    if ((float)(p - slack) == f && (float)(p + slack) == f) return f;
-    double s = 0.0;
-    for (uint32_t i = 0; i < n; i++) s += inc;
-    return (float)s;
-}
-
-__device__ __forceinline__ double per_kb_value_f64(uint32_t n, double inc) {
-    double s = 0.0;
-    for (uint32_t i = 0; i < n; i++) s += inc;  // exact replay; f64 output is a small-input path
-    return s;
-}
 
 enum OutKind { OUT_F32 = 0, OUT_F32_LOG2 = 1, OUT_U32 = 2, OUT_F64 = 3 };
 
@@ -231,11 +210,6 @@ struct CountArgs {
     void* out;                  // rows [n_seqs, 4^k] of the OUT type; TILES: uint32 [n_items, 4^k] partial histograms
     int k;
 };
-
-__device__ __forceinline__ void lds_add_u32(uint32_t* lds_base, uint32_t byte_addr, uint32_t v) {
-    (void)__hip_atomic_fetch_add(reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lds_base) + byte_addr), v, __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_WORKGROUP);  // result unused: ds_add_u32
-}
 
 // (Round 4 measured two other orders of the row flush — the row strictly in ascending address order, the hi pieces parked
 // in registers, with nontemporal or ordinary stores: 2 % at best at k = 6, 12-23 % slower at k = 7; DESIGN §4 — and

@@ -485,6 +485,7 @@ extern "C" int skr_seqs_free(skr_seqs* s) {
     if (s->d_len) (void)hipFree(s->d_len);
     if (s->d_mask) (void)hipFree(s->d_mask);
     if (s->d_mask_off) (void)hipFree(s->d_mask_off);
+    if (s->d_row_begin) (void)hipFree(s->d_row_begin);
     delete s;
     return SKR_OK;
 }

@@ -1,0 +1,229 @@
+"""k-mer profiles of sliding windows and `domain_pearson` on MI355X: which part of a long transcript or of a genomic region
+resembles a query.  The reference has no such function; the specification is an equivalence:
+
+    the row of a window equals, bit for bit, the row `BasicCounter` gives when the window's substring is handed to it as
+    a sequence of its own — same k, alphabet, log2, mean and std, same exceptions.
+
+No substring is made anywhere: the target is packed and uploaded once (2 bits per base) and every window is counted from
+the packed text at its base offset (`skr_count_windows_*`, csrc/windows.hip).  `domain_pearson` runs count -> normalise ->
+operand fill -> contraction one chunk of window rows at a time, so the window matrix (16 KiB a row at k = 6) never
+exists whole either.  Four distinct letters and k <= 7; anything else raises NotImplementedError.
+"""
+import os
+from collections import namedtuple
+
+import numpy as np
+
+from seekr_amd import _lib
+from seekr_amd import pearson as pearson_mod
+from seekr_amd.fasta_reader import Reader
+from seekr_amd.kmer_counts import NAN_WARNING, BasicCounter, _as_device_vector
+
+WindowCounts = namedtuple("WindowCounts", ["counts", "table", "mean", "std"])
+
+
+def window_table(lengths, window, slide):
+    """The windows of sequences of the given lengths: int64 arrays (seq_index, start, length), ordered by sequence, then by
+    start.  A sequence of length L has the starts j * slide for j = 0 ... ceil(max(L - window, 0) / slide); the window is
+    seq[start : start + window] as Python slices it, so the last one may be shorter and a sequence shorter than `window`
+    is one window."""
+    window, slide = int(window), int(slide)
+    if window < 1:
+        raise ValueError("window must be at least 1 (got {})".format(window))
+    if slide < 1:
+        raise ValueError("slide must be at least 1 (got {})".format(slide))
+    if slide > window:
+        raise ValueError("slide ({}) must not exceed window ({}): bases between two windows would be skipped".format(slide, window))
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    per_seq = np.where(lengths > window, (lengths - window + slide - 1) // slide + 1, 1)
+    first_row = np.zeros(len(lengths) + 1, dtype=np.int64)
+    np.cumsum(per_seq, out=first_row[1:])
+    seq_index = np.repeat(np.arange(len(lengths), dtype=np.int64), per_seq)
+    start = (np.arange(first_row[-1], dtype=np.int64) - first_row[seq_index]) * slide
+    length = np.minimum(window, lengths[seq_index] - start)
+    return seq_index, start, length
+
+
+def _holder(infasta_or_seqs, k, log2, alphabet):
+    """A BasicCounter that only holds the input: its constructor reads a FASTA file the way the reference does (and raises
+    what the reference raises), `seqs` assignment keeps the caller's strings as they are (lower case is then skipped)."""
+    if isinstance(infasta_or_seqs, (str, bytes, os.PathLike)):
+        holder = BasicCounter(os.fspath(infasta_or_seqs), k=k, mean=False, std=False, log2=log2, silent=True, alphabet=alphabet)
+    else:
+        holder = BasicCounter(k=k, mean=False, std=False, log2=log2, silent=True, alphabet=alphabet)
+        holder.seqs = list(infasta_or_seqs)
+    holder._check_k()
+    if not holder._two_bit:
+        raise NotImplementedError("windows are counted by the 2-bit kernels: an alphabet of four distinct letters is needed "
+                                  "(got {!r})".format(alphabet))
+    return holder
+
+
+def _headers(holder):
+    if holder.infasta is None:
+        return None
+    held = holder._packed if holder._packed is not None else holder._fasta
+    return held.headers() if held is not None else Reader(holder.infasta).get_headers()
+
+
+def _frame(columns):
+    from pandas import DataFrame
+    return DataFrame(columns)
+
+
+def _chunks(n_rows, chunk_rows):
+    chunk_rows = n_rows if not chunk_rows else max(1, int(chunk_rows))
+    return [(r0, min(chunk_rows, n_rows - r0)) for r0 in range(0, n_rows, max(chunk_rows, 1))]
+
+
+@_lib.api_call
+def window_counts(infasta_or_seqs, k, window, slide, mean=True, std=True, log2="Log2.post", alphabet="AGTC", chunk_rows=None):
+    """`BasicCounter(...).get_counts()` over the sliding windows of the input (a FASTA path, or a list of strings as assigned
+    to `BasicCounter.seqs`): WindowCounts(counts, table, mean, std).
+
+    counts: float32 [n_windows, 4^k], normalised as BasicCounter normalises the substrings — mean / std True: computed
+    over the windows; a path or an array: used as given; False: the step is skipped.  table: DataFrame with `seq_index`,
+    `start`, `length` (and `header` first for FASTA input).  mean, std: what BasicCounter leaves in `.mean` / `.std`.
+    chunk_rows: rows per counting launch (None: all at once); the rows do not depend on it.  The whole matrix stands on
+    the device here (the column statistics need it): `domain_pearson` is the form that does not."""
+    holder = _holder(infasta_or_seqs, k, log2, alphabet)
+    mean = np.load(mean) if isinstance(mean, str) else mean
+    std = np.load(std) if isinstance(std, str) else std
+    packed = holder._packed_seqs()
+    seq_index, start, length = window_table(packed.lengths(), window, slide)
+    n_rows = len(seq_index)
+    if n_rows == 1 and std is True:  # kmer_counts.py:124-130 on the substrings
+        raise ValueError("You cannot standardize a single sequence. Please pass the path to an std. dev. array, "
+                         "or use raw counts by setting std=False.")
+    ctx = holder._ctx()
+    dev = ctx.empty(n_rows, 4 ** k)
+    for r0, n in _chunks(n_rows, chunk_rows):
+        _lib.count_windows(ctx, packed, k, window, slide, r0, n, log2_pre=(log2 == "Log2.pre"),
+                           out=dev if n == n_rows else dev.view(r0, n))
+    mean_mode, mean_vec = 0, None
+    if mean is True:
+        mean_mode = 1
+    elif mean is not False:
+        mean_mode, mean_vec = 2, _as_device_vector(ctx, mean, dev.cols, dev.rows)
+    std_mode, std_vec = 0, None
+    if std is True:
+        std_mode = 1
+    elif std is not False:
+        std_mode, std_vec = 2, _as_device_vector(ctx, std, dev.cols, dev.rows)
+    # Log2.pre was fused into the counting flush, so the normaliser sees 'none' for it
+    mean_out, std_out, has_nan = _lib.normalize(ctx, dev, "Log2.post" if log2 == "Log2.post" else "Log2.none", mean_mode,
+                                                mean_vec, std_mode, std_vec)
+    if mean_out is not None:
+        mean = mean_out.vector()
+    if std_out is not None:
+        std = std_out.vector()
+    if has_nan:
+        print(NAN_WARNING)
+    columns = {"seq_index": seq_index, "start": start, "length": length}
+    headers = _headers(holder)
+    if headers is not None:
+        columns = dict(header=np.asarray(headers, dtype=object)[seq_index], **columns)
+    return WindowCounts(dev.to_numpy(), _frame(columns), mean, std)
+
+
+def _fixed_vector(vec, name):
+    if isinstance(vec, (str, os.PathLike)):
+        vec = np.load(vec)
+    if vec is None or isinstance(vec, (bool, np.bool_)):
+        raise ValueError("domain_pearson needs `{}` as a vector (an array or the path of a .npy file): the windows are "
+                         "normalised chunk by chunk, which is only defined with fixed vectors".format(name))
+    return vec
+
+
+class _Side:
+    """One operand of the chunked contraction in the layout asked for, refilled in float32 layout when a fill routes rows
+    there (skr_operand_kind: both operands of a contraction must have the same kind)."""
+
+    def __init__(self, ctx, rows, cols, precision):
+        self.ctx, self.rows, self.cols, self.precision = ctx, rows, cols, precision
+        self.ops = {}
+
+    def fill(self, x, precision, **tail):
+        op = self.ops.get(precision)
+        if op is None:
+            op = self.ops[precision] = _lib.Operand(self.ctx, self.rows, self.cols, precision)
+        view = op if x.rows == self.rows else op.view(0, x.rows)
+        _, has_nan = _lib.operand_fill(self.ctx, x, view, precision, want_nan=True, **tail)
+        return view, has_nan
+
+
+@_lib.api_call
+def domain_pearson(query, target, k, window, slide, mean, std, log2="Log2.post", chunk_rows=65536, outfile=None):
+    """Pearson r between every query and every sliding window of the target: (r float32 [n_query, n_windows], table).
+
+    query: a FASTA path (counted and normalised with `mean`, `std`, `log2` as BasicCounter does) or a normalised float32
+    count matrix [n_query, 4^k].  target: a FASTA path.  mean, std: vectors (arrays or .npy paths) — required.  Per chunk
+    of `chunk_rows` window rows: count -> normalise -> operand fill -> contraction against the query operand (filled
+    once) -> r[:, chunk]; one chunk of window counts is on the device at any time and no window text exists on the host.
+    With Log2.post the shift of kmer_counts.py:208 is the minimum over ALL windows, so the chunks are counted twice: once
+    for that minimum, once for r.  table: DataFrame with `header`, `start`, `end` of every window (the columns of r).
+    outfile: r is also saved there as .npy."""
+    mean, std = _fixed_vector(mean, "mean"), _fixed_vector(std, "std")
+    holder = _holder(target, k, log2, "AGTC")
+    if holder.infasta is None:
+        raise TypeError("domain_pearson takes the target as a FASTA path")
+    ctx = holder._ctx()
+    cols = 4 ** k
+    if isinstance(query, (str, bytes, os.PathLike)):
+        qc = BasicCounter(os.fspath(query), k=k, mean=mean, std=std, log2=log2, silent=True)
+        qc.get_counts()
+        qmat = qc.counts
+    else:
+        qmat = np.asarray(query)
+        if qmat.ndim != 2 or qmat.shape[1] != cols or qmat.dtype != np.float32:
+            raise ValueError("a query given as counts must be a float32 matrix of {} columns".format(cols))
+    packed = holder._packed_seqs()
+    seq_index, start, length = window_table(packed.lengths(), window, slide)
+    n_rows, n_query = len(seq_index), qmat.shape[0]
+    chunk_rows = max(1, min(int(chunk_rows), max(n_rows, 1)))
+    chunks = _chunks(n_rows, chunk_rows)
+    center, scale = _as_device_vector(ctx, mean, cols, None), _as_device_vector(ctx, std, cols, None)
+    cnt = ctx.empty(chunk_rows, cols)
+
+    def counted(r0, n):
+        out = cnt if n == chunk_rows else cnt.view(0, n)
+        return _lib.count_windows(ctx, packed, k, window, slide, r0, n, log2_pre=(log2 == "Log2.pre"), out=out)
+
+    post, shift, nan_seen = log2 == "Log2.post", np.float32(0.0), False
+    if post:  # np.min over the whole normalised matrix (NaN-propagating), chunk by chunk
+        lowest = np.float32(np.inf)
+        for r0, n in chunks:
+            mn, _ = _lib.min_nan(ctx, counted(r0, n), center, scale)
+            lowest = np.minimum(lowest, mn)
+        shift = np.abs(lowest)
+    precision = pearson_mod._precision_for(np.dtype(np.float32), True)
+    qdev = ctx.from_numpy(qmat)
+    qside, tside = _Side(ctx, n_query, cols, precision), _Side(ctx, chunk_rows, cols, precision)
+    q_op, _ = qside.fill(qdev, precision)
+    if q_op.kind == 0:
+        precision = _lib.PREC_FP32
+    r = np.empty((n_query, n_rows), dtype=np.float32)
+    r_dev = ctx.empty(n_query, chunk_rows)
+    for r0, n in chunks:
+        x = counted(r0, n)
+        tail = dict(center=center, scale=scale, post=post, shift=float(shift))
+        t_op, has_nan = tside.fill(x, precision, **tail)
+        a_op = q_op
+        if t_op.kind != q_op.kind:  # rows the split layouts do not carry: this chunk in float32 layout on both sides
+            t_op, has_nan = tside.fill(x, _lib.PREC_FP32, **tail)
+            a_op, _ = qside.fill(qdev, _lib.PREC_FP32)
+        nan_seen = nan_seen or has_nan
+        _lib.pearson_gemm_op(ctx, a_op, t_op, r_dev)
+        r[:, r0:r0 + n] = r_dev.to_numpy()[:, :n]
+    if nan_seen:
+        print(NAN_WARNING)
+    headers = np.asarray(_headers(holder), dtype=object)
+    table = _frame({"header": headers[seq_index] if n_rows else headers[:0], "start": start, "end": start + length})
+    if outfile:
+        _lib.save_npy(outfile, r)
+    return r, table
+
+
+def window_labels(table):
+    """`header:start-end` of every row of domain_pearson's table: the column labels of r in a labelled CSV."""
+    return ["{}:{}-{}".format(h, s, e) for h, s, e in zip(table["header"], table["start"], table["end"])]

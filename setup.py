@@ -16,6 +16,8 @@ setup(
             "seekr_pearson = seekr_amd.console_scripts:console_pearson",
             "seekr_norm_vectors = seekr_amd.console_scripts:console_norm_vectors",
             "seekr_adj_pval = seekr_amd.console_scripts:console_adj_pval",
+            # sliding windows of a target against queries (no counterpart in the reference)
+            "seekr_domain_pearson = seekr_amd.console_scripts:console_domain_pearson",
         ]
     },
 )
