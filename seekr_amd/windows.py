@@ -141,12 +141,17 @@ class _Side:
 
     def __init__(self, ctx, rows, cols, precision):
         self.ctx, self.rows, self.cols, self.precision = ctx, rows, cols, precision
-        self.ops = {}
+        self.ops, self.kinds = {}, {}
 
     def fill(self, x, precision, **tail):
         op = self.ops.get(precision)
+        if op is not None and op.kind != self.kinds[precision]:
+            # a full-size fill routed the cached operand itself, and skr_operand_fill keeps that kind: without a new operand
+            # every later chunk would be filled twice and contracted in float32 layout, whatever its rows are
+            op = None
         if op is None:
             op = self.ops[precision] = _lib.Operand(self.ctx, self.rows, self.cols, precision)
+            self.kinds[precision] = op.kind
         view = op if x.rows == self.rows else op.view(0, x.rows)
         _, has_nan = _lib.operand_fill(self.ctx, x, view, precision, want_nan=True, **tail)
         return view, has_nan
@@ -162,7 +167,8 @@ def domain_pearson(query, target, k, window, slide, mean, std, log2="Log2.post",
     once) -> r[:, chunk]; one chunk of window counts is on the device at any time and no window text exists on the host.
     With Log2.post the shift of kmer_counts.py:208 is the minimum over ALL windows, so the chunks are counted twice: once
     for that minimum, once for r.  table: DataFrame with `header`, `start`, `end` of every window (the columns of r).
-    outfile: r is also saved there as .npy."""
+    NAN_WARNING is printed once when a chunk's normalised counts or its block of r hold NaN.  outfile: r is also saved there
+    as .npy."""
     mean, std = _fixed_vector(mean, "mean"), _fixed_vector(std, "std")
     holder = _holder(target, k, log2, "AGTC")
     if holder.infasta is None:
@@ -215,6 +221,8 @@ def domain_pearson(query, target, k, window, slide, mean, std, log2="Log2.post",
         nan_seen = nan_seen or has_nan
         _lib.pearson_gemm_op(ctx, a_op, t_op, r_dev)
         r[:, r0:r0 + n] = r_dev.to_numpy()[:, :n]
+        # a constant row (a window of fewer than k letters under mean 0 / std 1) has finite counts and no r
+        nan_seen = nan_seen or bool(np.isnan(r[:, r0:r0 + n]).any())
     if nan_seen:
         print(NAN_WARNING)
     headers = np.asarray(_headers(holder), dtype=object)
