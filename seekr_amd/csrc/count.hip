@@ -20,6 +20,9 @@
 // window count differs from the previous item's) and streams the two 16-byte pieces of the dense row
 // with nontemporal stores — the row write (4*4^k bytes per sequence) is the algorithmic traffic that
 // bounds the kernel.
+// The bins, the sweep of a lane's pair of words, the flush and the LDS a launch asks for are count_bins.hpp's BinGeom,
+// sweep_pair, flush_row and row_launch_lds, shared with count_windows_kernel (windows.hip): what is written out below is
+// what this kernel has of its own — the persistent loop, the prefetch one item ahead and its hand-over, the tiles.
 //
 // Long sequences (more than 8 192 windows) are cut into tiles of 8 192 windows (the k-1 bases of halo
 // are simply the next packed words) that are counted like sequences into a scratch matrix of uint32
@@ -38,13 +41,11 @@
 #include <vector>
 
 #include "common.hpp"
-#include "per_kb.hpp"  // kTabSize, per_kb_value, per_kb_value_f64, lds_add_u32
+#include "count_bins.hpp"  // OutKind, BinGeom, sweep_pair, flush_row, per_kb_out, row_launch_lds (shared with windows.hip)
 
 namespace {
 
 constexpr int kThreads = 256;
-
-enum OutKind { OUT_F32 = 0, OUT_F32_LOG2 = 1, OUT_U32 = 2, OUT_F64 = 3 };
 
 template <int OUT, bool GLOBAL>
 __global__ __launch_bounds__(kThreads) void count_kmers_kernel(
@@ -115,14 +116,8 @@ __global__ __launch_bounds__(kThreads) void count_kmers_kernel(
         if (W == 0 && tid == 0) atomicOr(&flags[2], 1u);  // ZeroDivisionError in the reference
         if (GLOBAL) hist = reinterpret_cast<uint32_t*>(out) + (size_t)seq * nbins;  // 4-byte cells in every OUT handled here
         const int64_t n_win_words = W > 0 ? (W + 15) >> 4 : 0;
-        // the sequence's output value for every small count (almost all bins): 16 threads do the
-        // float64 work once, the flush just looks it up (visible after the barrier below)
         const double inc = W > 0 ? 1000.0 / (double)W : 0.0;
-        if (OUT != OUT_U32 && OUT != OUT_F64 && tid < kTabSize) {
-            float t = per_kb_value((uint32_t)tid, inc);
-            if (OUT == OUT_F32_LOG2) t = skr_log2_cr(t + 1.0f);  // kmer_counts.py:189-192: counts += 1; log2
-            tab[tid] = t;
-        }
+        build_value_table<OUT>(tab, tid, inc);  // visible after the barrier below
         const int j0 = (tid & 1) * 8;  // which half of the word's 16 windows this thread takes
         if ((tid >> 1) < n_win_words) {  // first sweep (2048 bases) from the prefetched registers
             const int64_t w = tid >> 1;
@@ -148,12 +143,7 @@ __global__ __launch_bounds__(kThreads) void count_kmers_kernel(
         __syncthreads();
 
         // ---- flush: bins -> per-kb values, dense row to HBM; the bins are zeroed on the way out
-        auto value_of = [&](uint32_t n) -> float {
-            if (n < (uint32_t)kTabSize) return tab[n];
-            float t = per_kb_value(n, inc);
-            if (OUT == OUT_F32_LOG2) t = skr_log2_cr(t + 1.0f);
-            return t;
-        };
+        auto value_of = [&](uint32_t n) -> float { return table_value<OUT>(tab, n, inc); };
         if (GLOBAL) {
             // the row holds this sequence's counts (written by L2 atomics: read them past the L1);
             // uint32 output is already in place, float output is converted where it stands
@@ -211,27 +201,17 @@ struct CountArgs {
     int k;
 };
 
-// (Round 4 measured two other orders of the row flush — the row strictly in ascending address order, the hi pieces parked
-// in registers, with nontemporal or ordinary stores: 2 % at best at k = 6, 12-23 % slower at k = 7; DESIGN §4 — and
-// removed them again: a lane step stores its lo piece and its hi piece back to back.)
+// (One wave per item: at least six waves per SIMD.  The Log2 instantiation's flush sits at the edge — 78 or 94 VGPRs with the
+// polarity of one branch — and the scheduler gives the sixth wave up unless it is asked for; the others have eight anyway.)
 template <int OUT, int WPS, bool TILES>
-__global__ __launch_bounds__(WPS * 64) void count_rows_kernel(const CountArgs a) {
+__global__ __launch_bounds__(WPS * 64) __attribute__((amdgpu_waves_per_eu(WPS == 1 ? 6 : 1))) void count_rows_kernel(const CountArgs a) {
     constexpr int T = WPS * 64;
     constexpr int P = WPS == 1 ? 2 : 1;  // sweeps of packed words prefetched one item ahead (2 048 / 4 096 bases)
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int tid = threadIdx.x;
     const int k = a.k;
-    const uint32_t nbins = 1u << (2 * k);
-    const uint32_t nwords = nbins >> 1;                 // two 16-bit bins per word: bin b and bin b + nwords
-    const uint32_t hist_words = nwords < 4 ? 4 : nwords;
-    uint32_t* hist = lds;                               // [hist_words] | trash [64] | tab [16]
-    const uint32_t trash_addr = (hist_words + (tid & 63)) * 4;  // one word per lane: no two lanes of a wave collide on it
-    float* tab = reinterpret_cast<float*>(lds + hist_words + 64);
-    const uint32_t sh = 30 - 2 * k;                     // (r >> sh) & amask = byte address of the window's word
-    const uint32_t amask = (nwords - 1) << 2;
-    const uint32_t win_mask = (1u << k) - 1u;           // k consecutive validity bits
-
-    for (uint32_t w = tid * 4; w < hist_words + 64; w += T * 4) *reinterpret_cast<uint4*>(&hist[w]) = make_uint4(0, 0, 0, 0);
+    const BinGeom<false> g(lds, k, tid);
+    g.template zero<T>(tid);
 
     // The packed words of the NEXT item are fetched while the current one is flushed.  Unconditional loads,
     // indices clamped into the padded arrays: a branch around them would make hipcc drain vmcnt(0) at the join.
@@ -282,59 +262,19 @@ __global__ __launch_bounds__(WPS * 64) void count_rows_kernel(const CountArgs a)
         const bool skip = !TILES && Wtot > kItemWindows;
         const int64_t nww = (Wi + 15) >> 4;
         const double inc = Wtot > 0 ? 1000.0 / (double)Wtot : 0.0;
-        if ((OUT == OUT_F32 || OUT == OUT_F32_LOG2) && Wtot != tab_W) {
-            // the item's output value for every small count (almost all bins): 16 lanes do the float64 work,
-            // the flush just looks it up; sets of equal-length sequences build it once
-            if (tid < kTabSize) {
-                float t = per_kb_value((uint32_t)tid, inc);
-                if (OUT == OUT_F32_LOG2) t = skr_log2_cr(t + 1.0f);  // kmer_counts.py:189-192: counts += 1; log2
-                tab[tid] = t;
-            }
+        if ((OUT == OUT_F32 || OUT == OUT_F32_LOG2) && Wtot != tab_W) {  // sets of equal-length sequences build it once
+            build_value_table<OUT>(g.tab, tid, inc);
             tab_W = Wtot;
         }
 
         auto sweep = [&](int64_t base, uint32_t hi, uint32_t lo) {
             const int64_t w = base + tid;
-            if (moff < 0 && Wi - ((base + T - 1) << 4) >= 16) {
-                // every lane of the workgroup has 16 whole windows.  Wave-level aggregation: if all 64 lanes
-                // hold the same two words, each of the 16 columns would get 64 adds on one address
-                const uint32_t h0 = __builtin_amdgcn_readfirstlane(hi), l0 = __builtin_amdgcn_readfirstlane(lo);
-                const bool same = __builtin_amdgcn_ballot_w64(((hi ^ h0) | (lo ^ l0)) != 0) == 0;
-                if (same) {
-                    if ((tid & 63) == 0) {
-#pragma unroll
-                        for (int j = 0; j < 16; j++) {
-                            const uint32_t r = j ? __builtin_amdgcn_alignbit(hi, lo, 32 - 2 * j) : hi;
-                            lds_add_u32(hist, (r >> sh) & amask, (int32_t)r < 0 ? 0x400000u : 64u);
-                        }
-                    }
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 16; j++) {
-                        const uint32_t r = j ? __builtin_amdgcn_alignbit(hi, lo, 32 - 2 * j) : hi;
-                        lds_add_u32(hist, (r >> sh) & amask, (int32_t)r < 0 ? 0x10000u : 1u);
-                    }
-                }
-            } else {
-                // a sweep that holds the end of the item or non-alphabet bases: windows that do not count are
-                // sent to a trash word (still counted in W: kmer_counts.py:143-149)
-                const int64_t left = Wi - (w << 4);
-                const int lim = left < 0 ? 0 : (left > 16 ? 16 : (int)left);
-                uint32_t invalid = 0;  // bit j: base 16(w0+w)+j is not in the alphabet
-                if (moff >= 0) {
-                    const int64_t aw = w0 + (w < nww ? w : nww);
-                    const uint32_t* mwords = a.mask + moff + (aw >> 1);
-                    invalid = (uint32_t)(((unsigned long long)mwords[0] | ((unsigned long long)mwords[1] << 32)) >> ((aw & 1) * 16));
-                }
-                if (lim > 0) {  // lanes past the end of the item do nothing
-#pragma unroll
-                    for (int j = 0; j < 16; j++) {
-                        const uint32_t r = j ? __builtin_amdgcn_alignbit(hi, lo, 32 - 2 * j) : hi;
-                        const bool ok = j < lim && ((invalid >> j) & win_mask) == 0;
-                        lds_add_u32(hist, ok ? ((r >> sh) & amask) : trash_addr, (int32_t)r < 0 ? 0x10000u : 1u);
-                    }
-                }
-            }
+            sweep_pair(g, tid, hi, lo, moff < 0 && Wi - ((base + T - 1) << 4) >= 16, Wi - (w << 4), [&]() -> uint32_t {
+                if (moff < 0) return 0;  // bit j: base 16(w0+w)+j is not in the alphabet
+                const int64_t aw = w0 + (w < nww ? w : nww);
+                const uint32_t* mwords = a.mask + moff + (aw >> 1);
+                return (uint32_t)(((unsigned long long)mwords[0] | ((unsigned long long)mwords[1] << 32)) >> ((aw & 1) * 16));
+            });
         };
 #pragma unroll
         for (int p = 0; p < P; p++)
@@ -355,57 +295,11 @@ __global__ __launch_bounds__(WPS * 64) void count_rows_kernel(const CountArgs a)
         if (WPS > 1) __syncthreads();
         else __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // one wave: the LDS executes its instructions in order
 
-        // ---- flush: bins -> output values, dense row to HBM; the bins are zeroed on the way out
+        // ---- flush: bins -> output values, dense row to HBM; the bins are zeroed on the way out for the next item
+        // (tiles are read again in a moment by reduce_tiles_kernel: ordinary stores leave them in the L2)
         if (!skip) {
-            auto value_of = [&](uint32_t n) -> float {
-                if (n < (uint32_t)kTabSize) return tab[n];
-                float t = per_kb_value(n, inc);
-                if (OUT == OUT_F32_LOG2) t = skr_log2_cr(t + 1.0f);
-                return t;
-            };
-            const size_t row = (size_t)(TILES ? it : seq) * nbins;
-            typedef float f4 __attribute__((ext_vector_type(4)));
-            typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-            for (uint32_t w4 = tid * 4; w4 < nwords; w4 += T * 4) {
-                const uint4 c = *reinterpret_cast<const uint4*>(&hist[w4]);
-                *reinterpret_cast<uint4*>(&hist[w4]) = make_uint4(0, 0, 0, 0);
-                if (nwords < 4) {  // k = 1: two words, four bins
-                    const uint32_t cw[2] = {c.x, c.y};
-                    for (int i = 0; i < 2; i++) {
-                        if (OUT == OUT_U32) {
-                            reinterpret_cast<uint32_t*>(a.out)[row + i] = cw[i] & 0xFFFFu;
-                            reinterpret_cast<uint32_t*>(a.out)[row + 2 + i] = cw[i] >> 16;
-                        } else {
-                            reinterpret_cast<float*>(a.out)[row + i] = value_of(cw[i] & 0xFFFFu);
-                            reinterpret_cast<float*>(a.out)[row + 2 + i] = value_of(cw[i] >> 16);
-                        }
-                    }
-                } else if (OUT == OUT_U32) {
-                    u4* dst = reinterpret_cast<u4*>(reinterpret_cast<uint32_t*>(a.out) + row + w4);
-                    const u4 lo4{c.x & 0xFFFFu, c.y & 0xFFFFu, c.z & 0xFFFFu, c.w & 0xFFFFu};
-                    const u4 hi4{c.x >> 16, c.y >> 16, c.z >> 16, c.w >> 16};
-                    if (TILES) {  // read again in a moment by reduce_tiles_kernel: leave them in the L2
-                        dst[0] = lo4;
-                        *reinterpret_cast<u4*>(reinterpret_cast<uint32_t*>(dst) + nwords) = hi4;
-                    } else {
-                        __builtin_nontemporal_store(lo4, dst);
-                        __builtin_nontemporal_store(hi4, reinterpret_cast<u4*>(reinterpret_cast<uint32_t*>(dst) + nwords));
-                    }
-                } else {
-                    f4 lo4, hi4;
-                    if (((c.x | c.y | c.z | c.w) & 0xFFF0FFF0u) == 0) {  // all eight counts below 16: table
-                        lo4 = f4{tab[c.x & 15u], tab[c.y & 15u], tab[c.z & 15u], tab[c.w & 15u]};
-                        hi4 = f4{tab[c.x >> 16], tab[c.y >> 16], tab[c.z >> 16], tab[c.w >> 16]};
-                    } else {
-                        lo4 = f4{value_of(c.x & 0xFFFFu), value_of(c.y & 0xFFFFu), value_of(c.z & 0xFFFFu), value_of(c.w & 0xFFFFu)};
-                        hi4 = f4{value_of(c.x >> 16), value_of(c.y >> 16), value_of(c.z >> 16), value_of(c.w >> 16)};
-                    }
-                    // the row is written once and not read again by this kernel: keep it out of the L2
-                    f4* dst = reinterpret_cast<f4*>(reinterpret_cast<float*>(a.out) + row + w4);
-                    __builtin_nontemporal_store(lo4, dst);
-                    __builtin_nontemporal_store(hi4, reinterpret_cast<f4*>(reinterpret_cast<float*>(dst) + nwords));
-                }
-            }
+            uint32_t* row = reinterpret_cast<uint32_t*>(a.out) + (size_t)(TILES ? it : seq) * g.nbins;  // 4-byte cells in every OUT
+            flush_row<OUT, false, true, TILES, T>(g, tid, row, inc);
         }
         if (WPS > 1) __syncthreads();  // zeroed bins visible before the next item is counted
         else __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -449,9 +343,7 @@ __global__ __launch_bounds__(256) void convert_long_kernel(const uint32_t* __res
         if (OUT == OUT_U32) {
             reinterpret_cast<uint32_t*>(out)[(size_t)seq * nbins + b] = n;
         } else {
-            float v = per_kb_value(n, inc);
-            if (OUT == OUT_F32_LOG2) v = skr_log2_cr(v + 1.0f);
-            reinterpret_cast<float*>(out)[(size_t)seq * nbins + b] = v;
+            reinterpret_cast<float*>(out)[(size_t)seq * nbins + b] = per_kb_out<OUT == OUT_F32_LOG2>(n, inc);
         }
     }
 }
@@ -460,7 +352,7 @@ __global__ __launch_bounds__(256) void convert_long_kernel(const uint32_t* __res
 template <int OUT, int WPS>
 int launch_rows(skr_ctx* ctx, const skr_seqs* s, int k, void* out) {
     const uint32_t nbins = 1u << (2 * k);
-    const size_t lds = ((size_t)std::max<uint32_t>(4u, nbins >> 1) + 64 + kTabSize) * 4;
+    const size_t lds = BinGeom<false>::lds_bytes(k);
     auto grid_for_kernel = [&](const void* kern, int threads, int64_t items, unsigned* grid) -> int {
         SKR_TRY(skr_kernel_lds(ctx, kern, lds));
         int per_cu = 0;
@@ -497,18 +389,9 @@ int launch_rows(skr_ctx* ctx, const skr_seqs* s, int k, void* out) {
     // bins every time, 0.63 against 0.70 of 8 TB/s for 20 000 x 2 kb)
     const bool persistent = ctx->knobs.count_persist == 1 || (ctx->knobs.count_persist == 0 && k >= 8);  // A/B knob
     if (!persistent) grid = (unsigned)std::min<int64_t>(s->n, 0x7fffffff);
-    size_t lds_launch = lds;
-    // Round 4: at k = 6 the LDS would let 19 one-wave workgroups share a CU; SEVENTEEN (enforced by asking for 9.25 KiB of
-    // LDS each) write the rows 7-8 % faster behind a contraction — 0.138-0.140 ms against 0.149-0.150 for 50 000 x 2 kb,
-    // 0.76 against 0.70 of 8 TB/s, two runs of tools/count_bench.py --pre gemm (profiles/r4_count_occupancy.log: 18 and 19
-    // per CU 0.150, 17 and 16 0.139, 15 and 14 0.146, 12 0.160, 8 0.187) — fewer row streams, no SIMD with a fifth wave
-    // for long.  Inside the bench step 17 measured 0.141-0.142 ms against 0.144-0.145 for 16 (two runs each), so 17 it is.
-    // Smaller k (2 KiB of bins and less) are fastest unrestricted.  SEEKR_COUNT_OCC overrides.
-    const int occ = ctx->knobs.count_occ > 0 ? ctx->knobs.count_occ : (WPS == 1 && k == 6 ? 17 : 0);
-    if (!persistent && occ > 0) {
-        lds_launch = std::max(lds, ((size_t)160 * 1024 / (size_t)occ) & ~(size_t)255);
-        SKR_TRY(skr_kernel_lds(ctx, reinterpret_cast<const void*>(kern), lds_launch));
-    }
+    // one workgroup per sequence: as many share a CU as measured fastest (count_bins.hpp: 17 at k = 6)
+    const size_t lds_launch = persistent ? lds : row_launch_lds<false>(ctx, WPS, k);
+    if (lds_launch != lds) SKR_TRY(skr_kernel_lds(ctx, reinterpret_cast<const void*>(kern), lds_launch));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(WPS * 64), lds_launch, ctx->stream, a);
     SKR_HIP(hipGetLastError());
     if (s->max_len - k + 1 <= kItemWindows) return SKR_OK;
@@ -676,9 +559,7 @@ __global__ __launch_bounds__(kThreads) void convert_generic_kernel(const uint32_
             } else if (std::is_same<OutT, uint32_t>::value) {
                 v = (OutT)n;
             } else {
-                float t = per_kb_value(n, inc);
-                if (LOG2) t = skr_log2_cr(t + 1.0f);
-                v = (OutT)t;
+                v = (OutT)per_kb_out<LOG2>(n, inc);
             }
             out[(size_t)(seq0 + s) * nbins + b] = v;
         }
@@ -789,9 +670,7 @@ __global__ __launch_bounds__(kGenThreads) __attribute__((amdgpu_num_vgpr(56), am
         const int64_t W = len - k + 1;  // windows, counting every character (kmer_counts.py:143-144)
         const double inc = W > 0 ? 1000.0 / (double)W : 0.0;
         if (!std::is_same<OutT, uint32_t>::value && sizeof(OutT) == 4 && tid < kTabSize) {
-            float t = per_kb_value((uint32_t)tid, inc);
-            if (LOG2) t = skr_log2_cr(t + 1.0f);
-            tab[tid] = t;
+            tab[tid] = per_kb_out<LOG2>((uint32_t)tid, inc);
         }
         for (int64_t c0 = 0; c0 < W; c0 += kGenChunk) {
             if (c0 > 0) {  // later chunks of a long sequence: translated here, into the buffer the first chunk came in
@@ -828,14 +707,7 @@ __global__ __launch_bounds__(kGenThreads) __attribute__((amdgpu_num_vgpr(56), am
         auto value_of = [&](uint32_t n) -> OutT {
             if (std::is_same<OutT, uint32_t>::value) return (OutT)n;
             if (sizeof(OutT) == 8) return (OutT)per_kb_value_f64(n, inc);
-            float t;
-            if (n < (uint32_t)kTabSize) {
-                t = tab[n];
-            } else {
-                t = per_kb_value(n, inc);
-                if (LOG2) t = skr_log2_cr(t + 1.0f);
-            }
-            return (OutT)t;
+            return (OutT)(n < (uint32_t)kTabSize ? tab[n] : per_kb_out<LOG2>(n, inc));
         };
         if (sizeof(OutT) == 4) {
             // Round 5: a group is four bins that are ALIGNED IN THE LDS (b = 4 g: one ds_read_b128, one ds_write_b128 of

@@ -21,6 +21,8 @@
 // streams 16-byte pieces of the dense row with nontemporal stores.  The row write — 4 * 4^k bytes per window against
 // window / 4 bytes read, most of them L2 hits, consecutive windows overlap — bounds the kernel.  One workgroup per row,
 // dispatched by the hardware in row order, as count_rows_kernel does it: the rows being written form a compact front.
+// Bins, sweep, flush and launch LDS are the shared code of count_bins.hpp; the kernel below is what a window adds: the
+// search in row_begin, the three-word funnel shift, the mask words at a base offset.
 // (Runs of 2 / 4 / 8 / 16 consecutive rows per workgroup, with the next row's words in flight across the flush, were
 // measured 3-7 % slower at 999 550 rows of k = 6 and removed: DESIGN section 4.)
 //
@@ -30,11 +32,9 @@
 #include <vector>
 
 #include "common.hpp"
-#include "per_kb.hpp"
+#include "count_bins.hpp"  // OutKind, BinGeom, sweep_pair, flush_row, row_launch_lds (shared with count.hip)
 
 namespace {
-
-enum OutKind { OUT_F32 = 0, OUT_F32_LOG2 = 1, OUT_U32 = 2 };
 
 struct WinArgs {
     const uint32_t* packed;
@@ -56,40 +56,26 @@ __global__ __launch_bounds__(WPS * 64) void count_windows_kernel(const WinArgs a
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int tid = threadIdx.x;
     const int k = a.k;
-    const uint32_t nbins = 1u << (2 * k);
-    const uint32_t nwords = WIDE ? nbins : nbins >> 1;  // WIDE: one 32-bit bin per word; else bin b and bin b + nwords share a word
-    const uint32_t hist_words = nwords < 4 ? 4 : nwords;
-    uint32_t* hist = lds;                               // [hist_words] | trash [64] | tab [16]
-    const uint32_t trash_addr = (hist_words + (tid & 63)) * 4;  // one word per lane: no two lanes of a wave collide on it
-    float* tab = reinterpret_cast<float*>(lds + hist_words + 64);
-    const uint32_t sh = 30 - 2 * k;                     // (r >> sh) & amask = byte address of the k-mer's word
-    const uint32_t amask = (nwords - 1) << 2;
-    const uint32_t win_mask = (1u << k) - 1u;           // k consecutive validity bits
-
+    const BinGeom<WIDE> g(lds, k, tid);
     const int64_t r = blockIdx.x;  // row of `out`
-    const int64_t g = a.first_row + r;
+    const int64_t gr = a.first_row + r;  // row of the table
+    g.template zero<T>(tid);
 
-    for (uint32_t w = tid * 4; w < hist_words + 64; w += T * 4) *reinterpret_cast<uint4*>(&hist[w]) = make_uint4(0, 0, 0, 0);
-
-    // the row's sequence: the last i with row_begin[i] <= g (every sequence has at least one row)
+    // the row's sequence: the last i with row_begin[i] <= gr (every sequence has at least one row)
     int64_t seq = 0;
     for (int64_t hi = a.n_seqs - 1; seq < hi;) {
         const int64_t mid = (seq + hi + 1) >> 1;
-        if (a.row_begin[mid] <= g) seq = mid;
+        if (a.row_begin[mid] <= gr) seq = mid;
         else hi = mid - 1;
     }
     const int64_t L = a.len[seq], moff = a.mask_off[seq];
-    const int64_t start = (g - a.row_begin[seq]) * a.slide;
+    const int64_t start = (gr - a.row_begin[seq]) * a.slide;
     const int64_t length = L - start < a.window ? L - start : a.window;  // seq[start : start + window]
     const int64_t Wtot = length - k + 1;  // k-mers, counting every character (kmer_counts.py:143-144)
     const int64_t Wn = Wtot > 0 ? Wtot : 0;
     const int64_t nww = (Wn + 15) >> 4;
     const double inc = Wtot > 0 ? 1000.0 / (double)Wtot : 0.0;
-    if ((OUT == OUT_F32 || OUT == OUT_F32_LOG2) && tid < kTabSize) {
-        float t = per_kb_value((uint32_t)tid, inc);
-        if (OUT == OUT_F32_LOG2) t = skr_log2_cr(t + 1.0f);  // kmer_counts.py:189-192: counts += 1; log2
-        tab[tid] = t;
-    }
+    build_value_table<OUT>(g.tab, tid, inc);
     const uint32_t bsh = (uint32_t)(start & 15) * 2;  // bit offset of the window's first base inside its packed word
     const uint32_t* words = a.packed + a.word_off[seq] + (start >> 4);
     if (WPS > 1) __syncthreads();  // bins zeroed
@@ -104,113 +90,26 @@ __global__ __launch_bounds__(WPS * 64) void count_windows_kernel(const WinArgs a
         // the 32 bases that start at base `start + 16 w`, first base in the top bits
         const uint32_t hi = bsh ? __builtin_amdgcn_alignbit(wa, wb, 32 - bsh) : wa;
         const uint32_t lo = bsh ? __builtin_amdgcn_alignbit(wb, wc3, 32 - bsh) : wb;
-        if (moff < 0 && Wn - ((base + T - 1) << 4) >= 16) {
-            // every lane of the workgroup has 16 whole k-mers.  Wave-level aggregation: if all 64 lanes hold the
-            // same two words, each of the 16 columns would get 64 adds on one address
-            const uint32_t h0 = __builtin_amdgcn_readfirstlane(hi), l0 = __builtin_amdgcn_readfirstlane(lo);
-            const bool same = __builtin_amdgcn_ballot_w64(((hi ^ h0) | (lo ^ l0)) != 0) == 0;
-            if (same) {
-                if ((tid & 63) == 0) {
-#pragma unroll
-                    for (int j = 0; j < 16; j++) {
-                        const uint32_t v = j ? __builtin_amdgcn_alignbit(hi, lo, 32 - 2 * j) : hi;
-                        lds_add_u32(hist, (v >> sh) & amask, WIDE ? 64u : ((int32_t)v < 0 ? 0x400000u : 64u));
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 16; j++) {
-                    const uint32_t v = j ? __builtin_amdgcn_alignbit(hi, lo, 32 - 2 * j) : hi;
-                    lds_add_u32(hist, (v >> sh) & amask, WIDE ? 1u : ((int32_t)v < 0 ? 0x10000u : 1u));
-                }
-            }
-        } else {
-            // a sweep that holds the end of the window or non-alphabet bases: k-mers that do not count are sent to a
-            // trash word (still counted in W: kmer_counts.py:143-149)
-            const int64_t left = Wn - (w << 4);
-            const int lim = left < 0 ? 0 : (left > 16 ? 16 : (int)left);
-            uint32_t invalid = 0;  // bit j: base start + 16 w + j is not in the alphabet
-            if (moff >= 0) {
-                const int64_t pbase = start + (wc << 4);
-                const uint32_t* mwords = a.mask + moff + (pbase >> 5);
-                invalid = (uint32_t)(((unsigned long long)mwords[0] | ((unsigned long long)mwords[1] << 32)) >> (pbase & 31));
-            }
-            if (lim > 0) {  // lanes past the end of the window do nothing
-#pragma unroll
-                for (int j = 0; j < 16; j++) {
-                    const uint32_t v = j ? __builtin_amdgcn_alignbit(hi, lo, 32 - 2 * j) : hi;
-                    const bool ok = j < lim && ((invalid >> j) & win_mask) == 0;
-                    lds_add_u32(hist, ok ? ((v >> sh) & amask) : trash_addr, WIDE ? 1u : ((int32_t)v < 0 ? 0x10000u : 1u));
-                }
-            }
-        }
+        sweep_pair(g, tid, hi, lo, moff < 0 && Wn - ((base + T - 1) << 4) >= 16, Wn - (w << 4), [&]() -> uint32_t {
+            if (moff < 0) return 0;  // bit j: base start + 16 w + j is not in the alphabet
+            const int64_t pbase = start + (wc << 4);
+            const uint32_t* mwords = a.mask + moff + (pbase >> 5);
+            return (uint32_t)(((unsigned long long)mwords[0] | ((unsigned long long)mwords[1] << 32)) >> (pbase & 31));
+        });
     }
     if (WPS > 1) __syncthreads();
     else __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 
-    // ---- flush: bins -> output values, dense row to HBM
-    auto value_of = [&](uint32_t n) -> float {
-        if (n < (uint32_t)kTabSize) return tab[n];
-        float t = per_kb_value(n, inc);
-        if (OUT == OUT_F32_LOG2) t = skr_log2_cr(t + 1.0f);
-        return t;
-    };
-    const size_t row = (size_t)r * nbins;
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-    for (uint32_t w4 = tid * 4; w4 < nwords; w4 += T * 4) {
-        const uint4 c = *reinterpret_cast<const uint4*>(&hist[w4]);
-        if (WIDE) {  // four bins of four words: one 16-byte piece (k = 1: the whole row)
-            if (OUT == OUT_U32) {
-                __builtin_nontemporal_store(u4{c.x, c.y, c.z, c.w}, reinterpret_cast<u4*>(reinterpret_cast<uint32_t*>(a.out) + row + w4));
-            } else {
-                __builtin_nontemporal_store(f4{value_of(c.x), value_of(c.y), value_of(c.z), value_of(c.w)},
-                                            reinterpret_cast<f4*>(reinterpret_cast<float*>(a.out) + row + w4));
-            }
-        } else if (nwords < 4) {  // k = 1: two words, four bins
-            const uint32_t cw[2] = {c.x, c.y};
-            for (int i = 0; i < 2; i++) {
-                if (OUT == OUT_U32) {
-                    reinterpret_cast<uint32_t*>(a.out)[row + i] = cw[i] & 0xFFFFu;
-                    reinterpret_cast<uint32_t*>(a.out)[row + 2 + i] = cw[i] >> 16;
-                } else {
-                    reinterpret_cast<float*>(a.out)[row + i] = value_of(cw[i] & 0xFFFFu);
-                    reinterpret_cast<float*>(a.out)[row + 2 + i] = value_of(cw[i] >> 16);
-                }
-            }
-        } else if (OUT == OUT_U32) {
-            u4* dst = reinterpret_cast<u4*>(reinterpret_cast<uint32_t*>(a.out) + row + w4);
-            __builtin_nontemporal_store(u4{c.x & 0xFFFFu, c.y & 0xFFFFu, c.z & 0xFFFFu, c.w & 0xFFFFu}, dst);
-            __builtin_nontemporal_store(u4{c.x >> 16, c.y >> 16, c.z >> 16, c.w >> 16},
-                                        reinterpret_cast<u4*>(reinterpret_cast<uint32_t*>(dst) + nwords));
-        } else {
-            f4 lo4, hi4;
-            if (((c.x | c.y | c.z | c.w) & 0xFFF0FFF0u) == 0) {  // all eight counts below 16: table
-                lo4 = f4{tab[c.x & 15u], tab[c.y & 15u], tab[c.z & 15u], tab[c.w & 15u]};
-                hi4 = f4{tab[c.x >> 16], tab[c.y >> 16], tab[c.z >> 16], tab[c.w >> 16]};
-            } else {
-                lo4 = f4{value_of(c.x & 0xFFFFu), value_of(c.y & 0xFFFFu), value_of(c.z & 0xFFFFu), value_of(c.w & 0xFFFFu)};
-                hi4 = f4{value_of(c.x >> 16), value_of(c.y >> 16), value_of(c.z >> 16), value_of(c.w >> 16)};
-            }
-            // the row is written once and not read again by this kernel: keep it out of the L2
-            f4* dst = reinterpret_cast<f4*>(reinterpret_cast<float*>(a.out) + row + w4);
-            __builtin_nontemporal_store(lo4, dst);
-            __builtin_nontemporal_store(hi4, reinterpret_cast<f4*>(reinterpret_cast<float*>(dst) + nwords));
-        }
-    }
+    // ---- flush: bins -> output values, dense row to HBM (one row per workgroup: nothing to zero, nothing read again)
+    flush_row<OUT, WIDE, false, false, T>(g, tid, reinterpret_cast<uint32_t*>(a.out) + (size_t)r * g.nbins, inc);
 }
 
 template <int OUT, int WPS, bool WIDE>
 int launch_windows(skr_ctx* ctx, const WinArgs& a, const char* name) {
     const int k = a.k;
-    const uint32_t nbins = 1u << (2 * k);
-    const size_t lds = ((size_t)std::max<uint32_t>(4u, WIDE ? nbins : nbins >> 1) + 64 + kTabSize) * 4;
     auto kern = count_windows_kernel<OUT, WPS, WIDE>;
-    size_t lds_launch = lds;
-    // k = 6, 16-bit bins: seventeen one-wave workgroups per CU, the number count_rows_kernel writes rows of this width
-    // fastest with (count.hip: launch_rows), enforced the same way — by the LDS asked for
-    const int occ = ctx->knobs.count_occ > 0 ? ctx->knobs.count_occ : (WPS == 1 && k == 6 && !WIDE ? 17 : 0);
-    if (occ > 0) lds_launch = std::max(lds, ((size_t)160 * 1024 / (size_t)occ) & ~(size_t)255);
+    // as many workgroups per CU as count_rows_kernel writes rows of this width fastest with (count_bins.hpp: 17 at k = 6)
+    const size_t lds_launch = row_launch_lds<WIDE>(ctx, WPS, k);
     SKR_TRY(skr_kernel_lds(ctx, reinterpret_cast<const void*>(kern), lds_launch));
     SKR_REQUIRE(a.n_rows <= 0x7fffffff, "%lld rows in one call: count them in runs", (long long)a.n_rows);
     SkrProfScope prof(ctx, name);

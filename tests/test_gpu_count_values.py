@@ -1,5 +1,5 @@
-"""The float32 per-kb value of every counting kernel (count.hip: per_kb_value, ten call sites in six kernels) at the pairs
-(count, windows) of tests/golden/count_value_pairs.json — where float32(n * inc) is not the float32 of the reference's
+"""The float32 per-kb value of every counting kernel (per_kb.hpp: per_kb_value, which six kernels reach through per_kb_out
+of count_bins.hpp) at the pairs (count, windows) of tests/golden/count_value_pairs.json — where float32(n * inc) is not the float32 of the reference's
 running sum, where only the slack test fires, inside the 16-entry tables — and the launch boundaries of the same file
 (tile batches, gridDim.y, the any-alphabet HBM path in several batches), as tools/count_value_sweep.py walks them.  Bit-exact
 against the C oracle, Log2.pre within the bar of test_gpu_parity.py.  Needs a real MI355X: run with `-m gpu`."""

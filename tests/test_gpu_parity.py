@@ -436,6 +436,32 @@ def test_long_sequences_are_cut_into_tiles(k, L, ctx):
     assert np.allclose(got_pre, want_pre, rtol=RTOL, atol=ATOL_LOG)
 
 
+@pytest.mark.parametrize("k", [1, 2])
+def test_tiles_and_rows_of_the_smallest_k(k, L, ctx):
+    """The row flush (count_bins.hpp: flush_row) at k = 1 — two packed words, fewer than the four a lane step reads — and
+    k = 2, in its zero-on-the-way-out arm (sequences) and its tile arm (ordinary stores), which only a sequence of more
+    than 8 192 windows reaches at these k: one window, 40 bases, exactly one tile, two tiles of which the second holds one
+    window (once with an N next to the boundary), a homopolymer of two tiles.  Raw counts and per-kb float32 bit for bit
+    against the C oracle, Log2.pre within the bar of this file."""
+    from oracle import c_oracle as co
+    rng = np.random.default_rng(200 + k)
+    letters = np.frombuffer(b"ACGT", dtype=np.uint8)
+    arrs = [letters[rng.integers(0, 4, size=n)].copy() for n in (k, 40, 8192 + k - 1, 8193 + k - 1, 8193 + k - 1)]
+    arrs[-1][8190] = ord("N")
+    arrs.append(np.full(9000, ord("G"), np.uint8))
+    seqs = [a.tobytes().decode() for a in arrs]
+    lens = [len(s) for s in seqs]
+    blob, offsets = co.seqs_to_blob(seqs)
+    n_ref = co.count_u32(blob, offsets, k)
+    assert [int(r.sum()) for r in n_ref] == [1, 41 - k, 8192, 8193, 8193 - k, 9001 - k]  # the N voids the k k-mers over it
+    packed = ctx.pack(seqs, "AGTC")
+    assert np.array_equal(L.count_u32(ctx, packed, k).to_numpy(), n_ref)
+    want = co.per_kb_f32(n_ref, lens, k)
+    assert_bits(L.count_per_kb(ctx, packed, k).to_numpy(), want, "per-kb of one and two tiles, k=%d" % k)
+    got_pre = L.count_per_kb(ctx, packed, k, log2_pre=True).to_numpy()
+    assert np.allclose(got_pre, orc.log2_plus_one(want), rtol=RTOL, atol=ATOL_LOG)
+
+
 def test_normalize_bitexact_vs_oracle_odd_shapes(L, ctx):
     rng = np.random.default_rng(3)
     for rows, cols in ((7, 4), (300, 16), (1025, 64), (513, 100), (2500, 1024)):

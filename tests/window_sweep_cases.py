@@ -1,6 +1,6 @@
 """Cases of the window sweep (tests/test_gpu_window_sweep.py, tests/test_window_sweep_cpu.py) — test infrastructure.
 
-count_windows_kernel (csrc/windows.hip) has a fast branch for sweeps in which every lane of the workgroup holds 16 whole
+count_windows_kernel (csrc/windows.hip; its sweep is sweep_pair of csrc/count_bins.hpp) has a fast branch for sweeps in which every lane of the workgroup holds 16 whole
 k-mers of an all-alphabet sequence, and inside it an aggregated arm for sweeps whose 64 lanes hold the same 32 bases
 (homopolymers, repeats whose period divides 16).  The cases here are built to reach them: windows of one and two full
 sweeps, repeats of every such period with controls, bins that end at exactly 65 535 and 65 536, one N at every phase, runs
@@ -30,7 +30,7 @@ def sweep_bases(k):
 
 
 def fast_sweeps(window, k):
-    """How many sweeps of a full window of an all-alphabet sequence take the fast branch (windows.hip:107)."""
+    """How many sweeps of a full window of an all-alphabet sequence take the fast branch (count_bins.hpp: the `whole` arm of sweep_pair)."""
     return max(window - k + 1, 0) // (16 * threads(k))
 
 

@@ -2,7 +2,7 @@
 arithmetic part ways, and the launch boundaries of the same file.
 
 The reference stores float32(n sequential float64 additions of 1000 / W) for a k-mer seen n times in a sequence of W
-windows (kmer_counts.py:144-150).  count.hip: per_kb_value returns float32(n * (1000 / W)) and replays the additions only
+windows (kmer_counts.py:144-150).  per_kb.hpp: per_kb_value returns float32(n * (1000 / W)) and replays the additions only
 when the product lies within p (n + 4) 2^-53 of a float32 rounding boundary.  tests/golden/count_value_pairs.json
 (make_golden_count_pairs.py) holds pairs (n, W) where the two differ (`mismatch`: the first one is n = 35 604, W = 35 747),
 where the slack test fires for nothing (`guard_only`), where it fires inside the kernels' 16-entry tables (`small_n`) and
@@ -50,7 +50,7 @@ RTOL, ATOL_LOG = 1e-5, 1e-6  # tests/test_gpu_parity.py: the bar of every Log2.p
 ITEM_WINDOWS = 8192          # count.hip kItemWindows
 GEN_CHUNK = 4096             # count.hip kGenChunk
 GEN_LDS_BINS = 36864         # count.hip kGenLdsBins
-TAB_SIZE = 16                # count.hip kTabSize
+TAB_SIZE = 16                # per_kb.hpp kTabSize
 W_BIG = 5_000_000
 AMINO = "ARNDCQEGHILKMFPSTWYV"
 
@@ -107,7 +107,7 @@ def scan_w(W):
 
 
 def per_kb_model(n, W, sums=None):
-    """count.hip: per_kb_value restated: the product, unless n > 3 and the slack test fires — then the replayed sum.
+    """per_kb.hpp: per_kb_value restated: the product, unless n > 3 and the slack test fires — then the replayed sum.
     n: int64 array of counts <= W.  Returns (float32 values, which of them were replayed)."""
     n = np.asarray(n, dtype=np.int64)
     fire, f, s32 = evaluate(n, 1000.0 / W, (running_sums(W) if sums is None else sums)[n])
