@@ -36,22 +36,45 @@ __device__ __forceinline__ _Float16 split_hi_f16(float zs, uint32_t flip) {
     return __builtin_bit_cast(_Float16, (uint16_t)(bits ^ (uint16_t)(flip >> 16)));
 }
 template <typename T>
-__device__ __forceinline__ T split_hi(float zs, int64_t col) {
-    return (T)zs;  // hardware convert: RNE, NaN stays NaN
-}
-template <>
-__device__ __forceinline__ _Float16 split_hi<_Float16>(float zs, int64_t col) {
-    return split_hi_f16(zs, split_flip(col));
-}
-// ... and with the direction of the cell known to the caller (the register kernel keeps one bit per cell of its lane)
-template <typename T>
 __device__ __forceinline__ T split_hi_flip(float zs, uint32_t flip) {
-    return (T)zs;
+    return (T)zs;  // hardware convert: RNE, NaN stays NaN
 }
 template <>
 __device__ __forceinline__ _Float16 split_hi_flip<_Float16>(float zs, uint32_t flip) {
     return split_hi_f16(zs, flip);
 }
+
+template <typename T, int N>
+using halves = T __attribute__((ext_vector_type(N)));
+
+// The split of N cells (4 or 8) of a row, the one copy every fill kernel uses: zs = z x out_scale (a power of two: exact),
+// hi = zs rounded in the direction flip_of(j) gives for cell j (split_flip of the cell's column, or a bit of a DirBits the
+// thread made once per launch), lo = the exact difference rounded to nearest.  SplitNearest in place of flip_of: hi to
+// nearest (the f16f8 lines).  Returns whether a |zs| left the fp16 range.
+struct SplitNearest {};
+template <typename T, int N, class Flip>
+__device__ __forceinline__ bool split_cells(const float (&z)[N], float out_scale, Flip flip_of, halves<T, N>& hi, halves<T, N>& lo) {
+    bool overflow = false;
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        const float zs = z[j] * out_scale;
+        if (fabsf(zs) > 65504.f) overflow = true;
+        T hh;
+        if constexpr (std::is_same<Flip, SplitNearest>::value) hh = (T)zs;
+        else hh = split_hi_flip<T>(zs, flip_of(j));
+        hi[j] = hh;
+        lo[j] = (T)(zs - (float)hh);  // exact difference, then RNE
+    }
+    return overflow;
+}
+// Rounding direction of the hi half of each of the CELLS cells a thread owns in every row, one bit per cell (a hash of the
+// COLUMN: the same for every row) — the kernels that hold a row in registers build it once per launch.
+template <int CELLS>
+struct DirBits {
+    uint32_t w[(CELLS + 31) / 32] = {};
+    __device__ __forceinline__ void set(int cell, int64_t col) { w[cell >> 5] |= (split_flip(col) >> 31) << (cell & 31); }
+    __device__ __forceinline__ uint32_t flip(int cell) const { return (w[cell >> 5] << (31 - (cell & 31))) & 0x80000000u; }
+};
 
 // x / d for float32 x and d, rounded exactly as the IEEE division rounds it, from r = RN64(1 / d): the product
 // RN64(x * r) is within 2^-52 (relative) of x / d, and a quotient of two float32 numbers that is not itself a float32
@@ -60,9 +83,6 @@ __device__ __forceinline__ _Float16 split_hi_flip<_Float16>(float zs, uint32_t f
 // way the exact quotient does.  Zero, infinite and NaN divisors behave as in x / d (r = inf, 0, NaN).  Three
 // instructions instead of the ten of v_div_scale / v_rcp / 4 fma / v_div_fmas / v_div_fixup.
 __device__ __forceinline__ float div_by_recip(float x, double r) { return (float)((double)x * r); }
-
-template <typename T>
-using vec8 = T __attribute__((ext_vector_type(8)));
 
 // Wave-wide sums and maxima on the DPP network (round 5; until then a __shfl_xor butterfly, i.e. a ds_bpermute — an LDS
 // operation — per step, six dependent steps a sum): four DPP steps leave every lane of a 16-lane row with its row's total,
@@ -73,25 +93,17 @@ __device__ __forceinline__ float dpp_step_c(float v) {
     const float o = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
     return IS_MAX ? fmaxf(v, o) : v + o;
 }
-template <bool IS_MAX>
-__device__ __forceinline__ float row16_all(float v) {  // every lane: the reduction over its row of 16 lanes
+template <bool IS_MAX, int N>
+__device__ __forceinline__ float rowN_all(float v) {  // every lane: the reduction over its 16 (or 8) neighbouring lanes
     v = dpp_step_c<IS_MAX, 0xB1>(v);   // quad_perm [1,0,3,2]
     v = dpp_step_c<IS_MAX, 0x4E>(v);   // quad_perm [2,3,0,1]
     v = dpp_step_c<IS_MAX, 0x141>(v);  // row_half_mirror
-    v = dpp_step_c<IS_MAX, 0x140>(v);  // row_mirror
-    return v;
-}
-template <bool IS_MAX, int N>
-__device__ __forceinline__ float rowN_all(float v) {  // every lane: the reduction over its 16 (or 8) neighbouring lanes
-    v = dpp_step_c<IS_MAX, 0xB1>(v);
-    v = dpp_step_c<IS_MAX, 0x4E>(v);
-    v = dpp_step_c<IS_MAX, 0x141>(v);
-    if (N == 16) v = dpp_step_c<IS_MAX, 0x140>(v);
+    if (N == 16) v = dpp_step_c<IS_MAX, 0x140>(v);  // row_mirror
     return v;
 }
 template <bool IS_MAX>
 __device__ __forceinline__ float wave64_all(float v) {  // every lane: the reduction over the wave
-    v = row16_all<IS_MAX>(v);
+    v = rowN_all<IS_MAX, 16>(v);
     const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
     const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
     return IS_MAX ? fmaxf(fmaxf(r0, r1), fmaxf(r2, r3)) : (r0 + r1) + (r2 + r3);
@@ -268,20 +280,76 @@ __device__ __forceinline__ bool row_on_two_levels(float var, float m3, float m4)
     const float sk = m3 / (var * sqrtf(var)), ku = m4 / (var * var);
     return ku - sk * sk - 1.0f < 5e-3f;  // false for NaN rows
 }
-
+// one cell's share of the row's sums of z^2 (the diagonal; an explicit FMA: every kernel rounds this sum the same way) and,
+// for halves, of z^3 and z^4 (row_on_two_levels)
+template <bool HALVES>
+__device__ __forceinline__ void add_moments(float v, float& sq, float& m3, float& m4) {
+    sq = __fmaf_rn(v, v, sq);
+    if (HALVES) {
+        const float v2 = v * v;
+        m3 = fmaf(v2, v, m3);
+        m4 = fmaf(v2, v2, m4);
+    }
+}
+// the largest z^2 of a row sits at its largest or its smallest value: rounding is monotone, so these two evaluations are
+// what the maximum over all cells would be (NaN cells never counted; a row without a finite value: 0)
+__device__ __forceinline__ float zmax2_of_extremes(float vmin, float vmax, float mean, float sd) {
+    float zmax2 = 0.f;
+    if (vmin <= vmax) {
+        const float z_lo = (vmin - mean) / sd, z_hi = (vmax - mean) / sd;
+        zmax2 = fmaxf(z_lo * z_lo, z_hi * z_hi);
+        if (!(zmax2 == zmax2)) zmax2 = 0.f;
+    }
+    return zmax2;
+}
+// Rows that are mostly ONE value are 'coherent'.  Near-copies of such a row have only positive products, small ones added
+// to a sum that is already large, and the truncating accumulate then loses up to an ulp of the sum per add
+// (tools/margin_probe.py: the bar is reached at 97 %); the contraction restarts its accumulators twice as often for flagged
+// operands.  The value is the row's minimum (count data: the empty bins; `same` = cells equal to it; equal raw values give
+// equal z) or ANY one value (round 4: a centred row repeats 0, not its minimum — the differential fuzzer's soak found
+// r = -0.46 off by 1.07 bars on rows that were 89 % zeros): if one value fills 85 % of the cells, at least 70 % of the
+// neighbouring pairs are equal (each other cell spoils two pairs at most), whatever the value is (`adj` = equal pairs).
+constexpr float kOneValueShare = 0.85f, kEqualPairShare = 0.70f;
+// ... the register kernel sees only the three pairs INSIDE each group of four cells a lane holds: 85 % of one value
+// leaves at least 0.45 K of those equal
+constexpr float kEqualPairShareInQuads = 0.45f;
+// (a statement, not a predicate: with the verdict returned as a bool the sixteen-wave block kernel for fp16 halves came out
+// at 102 instead of 91 registers and lost its fifth wave)
+template <class I>
+__device__ __forceinline__ void flag_mostly_one_value(float same, float adj, I K, bool& coherent) {
+    if (same >= kOneValueShare * (float)K || adj >= kEqualPairShare * (float)(K - 1)) coherent = true;
+}
+// what a thread has seen in its rows, ORed into the launch's flags at the end of the kernel: [1] NaN seen, [3] fp16 range
+// exceeded, [4] a row needs more dynamic range than one float32 accumulator per cell has, [5] a coherent row, [6] (f16f8
+// lines only) a row repeats values
+struct RowFlags {
+    bool any_nan = false, overflow = false, outlier = false, coherent = false, repeats = false;
+    __device__ __forceinline__ void flush(uint32_t* flags) const {
+        if (any_nan) atomicOr(&flags[1], 1u);
+        if (overflow) atomicOr(&flags[3], 1u);
+        if (outlier) atomicOr(&flags[4], 1u);
+        if (coherent) atomicOr(&flags[5], 1u);
+        if (repeats) atomicOr(&flags[6], 1u);
+    }
+};
+// Pass 3 of the wave-per-row and the workgroup-per-row kernel (mask, standardise, moments, split and store of 8 cells) is
+// written out in each of the two: as one emit_group8 helper it had the parent's registers and occupancy or better, and was
+// slower in two of its three users — 50 000 x 2 401 bare 1.257 -> 1.267 ms (wave per row) and 10 000 x 40 004 with vectors,
+// Log2.post and y 5.066 -> 5.080 ms (1 024-thread workgroup per row; with only the cell loop written out and add_moments /
+// split_cells called: bare 3.427 -> 3.462 ms).  Samples: profiles/operand_fill_refactor_ab.json, findings_fixed.
 template <typename T>
 __global__ __launch_bounds__(256) void operand_fill_kernel(FillArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
-    const int64_t K = a.cols, Kp = a.kt * 32;
+    const int64_t K = a.cols;
     float* row = lds + (size_t)wave * ((K + 3) & ~(int64_t)3);
     const bool vec = (K & 3) == 0;
     // numpy-ordered row sums (above): the plan lives behind the row slices, one per wave
     const NpPlan* plan = a.np_plan;
     const bool np_exact = a.row_standardize && plan != nullptr;
     NpScratch* np_sc = reinterpret_cast<NpScratch*>(lds + (size_t)waves * ((K + 3) & ~(int64_t)3)) + wave;
-    bool any_nan = false, overflow = false, outlier = false, coherent = false;
+    RowFlags seen;
     for (int64_t r = (int64_t)blockIdx.x * waves + wave; r < a.rows; r += (int64_t)gridDim.x * waves) {
         const float* xr = a.x + (size_t)r * K;
         // ---- pass 1: load, elementwise tail of the normalisation, optional write-back, row sum
@@ -289,17 +357,17 @@ __global__ __launch_bounds__(256) void operand_fill_kernel(FillArgs a) {
         if (vec) {
             for (int64_t c = lane * 4; c < K; c += 256) {
                 float4 v = *reinterpret_cast<const float4*>(xr + c);
-                v.x = fill_tail(a, v.x, c, any_nan);
-                v.y = fill_tail(a, v.y, c + 1, any_nan);
-                v.z = fill_tail(a, v.z, c + 2, any_nan);
-                v.w = fill_tail(a, v.w, c + 3, any_nan);
+                v.x = fill_tail(a, v.x, c, seen.any_nan);
+                v.y = fill_tail(a, v.y, c + 1, seen.any_nan);
+                v.z = fill_tail(a, v.z, c + 2, seen.any_nan);
+                v.w = fill_tail(a, v.w, c + 3, seen.any_nan);
                 if (a.y) *reinterpret_cast<float4*>(a.y + (size_t)r * K + c) = v;
                 *reinterpret_cast<float4*>(row + c) = v;
                 s += (v.x + v.y) + (v.z + v.w);
             }
         } else {
             for (int64_t c = lane; c < K; c += 64) {
-                const float v = fill_tail(a, xr[c], c, any_nan);
+                const float v = fill_tail(a, xr[c], c, seen.any_nan);
                 if (a.y) a.y[(size_t)r * K + c] = v;
                 row[c] = v;
                 s += v;
@@ -341,19 +409,16 @@ __global__ __launch_bounds__(256) void operand_fill_kernel(FillArgs a) {
                 zmax2 = fmaxf(zmax2, zc * zc);
             }
             zmax2 = wave_max(zmax2);
-            // share of the row held by its minimum (see operand_fill_reg_kernel); equal raw values give equal z
+            // share of the row held by its minimum, or by any one value (flag_mostly_one_value)
             float vmin = row[0];
             for (int64_t c = lane; c < K; c += 64) vmin = fminf(vmin, row[c]);
             vmin = -wave_max(-vmin);
-            // ... or by ANY one value (round 4: a centred row repeats 0, not its minimum — the differential fuzzer's soak found
-            // r = -0.46 off by 1.07 bars on rows that were 89 % zeros): if one value fills 85 % of the cells, at least 70 % of
-            // the neighbouring pairs are equal (each other cell spoils two pairs at most), whatever the value is
             float same = 0.f, adj = 0.f;
             for (int64_t c = lane; c < K; c += 64) {
                 same += (float)(row[c] == vmin);
                 if (c + 1 < K) adj += (float)(row[c] == row[c + 1]);
             }
-            if (wave_sum(same) >= 0.85f * (float)K || wave_sum(adj) >= 0.70f * (float)(K - 1)) coherent = true;
+            flag_mostly_one_value(wave_sum(same), wave_sum(adj), K, seen.coherent);
         }
         // ---- pass 3: emit the operand row, 8 k per lane and step
         float sq = 0.f, m3 = 0.f, m4 = 0.f;
@@ -374,34 +439,31 @@ __global__ __launch_bounds__(256) void operand_fill_kernel(FillArgs a) {
                 }
             }
             if (sizeof(T) == 4) {
-                float* dst = reinterpret_cast<float*>(a.out) + (size_t)r * Kp + k0;
+                float* dst = reinterpret_cast<float*>(a.out) + (size_t)r * (a.kt * 32) + k0;
                 *reinterpret_cast<float4*>(dst) = make_float4(z[0], z[1], z[2], z[3]);
                 *reinterpret_cast<float4*>(dst + 4) = make_float4(z[4], z[5], z[6], z[7]);
             } else {
-                vec8<T> hi, lo;
+                halves<T, 8> hi, lo;
 #pragma unroll
                 for (int j = 0; j < 8; j++) {
                     const float zs = z[j] * a.out_scale;
-                    if (fabsf(zs) > 65504.f) overflow = true;
-                    const T hh = split_hi<T>(zs, k0 + j);
+                    if (fabsf(zs) > 65504.f) seen.overflow = true;
+                    const T hh = split_hi_flip<T>(zs, split_flip(k0 + j));
                     hi[j] = hh;
-                    lo[j] = (T)(zs - (float)hh);        // exact difference, then RNE
+                    lo[j] = (T)(zs - (float)hh);
                 }
                 T* dst = reinterpret_cast<T*>(a.out) + ((size_t)r * a.kt + tile) * 64 + sub * 8;
-                *reinterpret_cast<vec8<T>*>(dst) = hi;
-                *reinterpret_cast<vec8<T>*>(dst + 32) = lo;
+                *reinterpret_cast<halves<T, 8>*>(dst) = hi;
+                *reinterpret_cast<halves<T, 8>*>(dst + 32) = lo;
             }
         }
         sq = wave_sum(sq);
         if (lane == 0) a.diag[r] = sq / (float)K;
         if (sizeof(T) != 4 && a.row_standardize && row_on_two_levels(sq / (float)K, wave_sum(m3) / (float)K, wave_sum(m4) / (float)K))
-            coherent = true;
-        if (sizeof(T) != 4 && row_needs_fp32(zmax2, (float)K)) outlier = true;
+            seen.coherent = true;
+        if (sizeof(T) != 4 && row_needs_fp32(zmax2, (float)K)) seen.outlier = true;
     }
-    if (any_nan) atomicOr(&a.flags[1], 1u);
-    if (overflow) atomicOr(&a.flags[3], 1u);
-    if (outlier) atomicOr(&a.flags[4], 1u);
-    if (coherent) atomicOr(&a.flags[5], 1u);
+    seen.flush(a.flags);
 }
 
 // One WORKGROUP per row, for rows of 32 KiB and more (k >= 7), where a wave-private LDS slice would
@@ -419,18 +481,24 @@ __global__ __launch_bounds__(THREADS) void operand_fill_block_kernel(FillArgs a)
     constexpr int WAVES = THREADS / 64;
     __shared__ float red[WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t K = a.cols, Kp = a.kt * 32, groups = a.kt * 4;
+    const int64_t K = a.cols, groups = a.kt * 4;
     const bool vec = (K & 7) == 0;
-    bool any_nan = false, overflow = false, outlier = false, coherent = false;
-    auto block_sum = [&](float v) -> float {
-        v = wave_sum(v);
+    RowFlags seen;
+    // the sum or the maximum (a minimum: of the negated values) over the workgroup; every thread gets it
+    auto block_all = [&](float v, auto max_) -> float {
+        constexpr bool IS_MAX = decltype(max_)::value;
+        auto op = [](float x, float y) { return IS_MAX ? fmaxf(x, y) : x + y; };
+        v = wave64_all<IS_MAX>(v);
         if (lane == 0) red[wave] = v;
         __syncthreads();
-        float t = (red[0] + red[1]) + (red[2] + red[3]);
-        if (WAVES == 16) t = (t + ((red[4] + red[5]) + (red[6] + red[7]))) + (((red[8] + red[9]) + (red[10] + red[11])) + ((red[12] + red[13]) + (red[14] + red[15])));
+        const float* w = red;  // (sixteen partials only where there are sixteen waves)
+        float t = op(op(w[0], w[1]), op(w[2], w[3]));
+        if (WAVES == 16) t = op(op(t, op(op(w[4], w[5]), op(w[6], w[7]))), op(op(op(w[8], w[9]), op(w[10], w[11])), op(op(w[12], w[13]), op(w[14], w[15]))));
         __syncthreads();
         return t;
     };
+    auto block_sum = [&](float v) -> float { return block_all(v, std::false_type()); };
+    auto block_max = [&](float v) -> float { return block_all(v, std::true_type()); };
     typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
     const int64_t n4 = K >> 2;
     for (int64_t r = blockIdx.x; r < a.rows; r += gridDim.x) {
@@ -478,10 +546,10 @@ __global__ __launch_bounds__(THREADS) void operand_fill_block_kernel(FillArgs a)
                     if (i < n4) {
                         const int64_t c = 4 * i;
                         f4u w;
-                        w[0] = fill_tail(a, q[u][0], c, any_nan);
-                        w[1] = fill_tail(a, q[u][1], c + 1, any_nan);
-                        w[2] = fill_tail(a, q[u][2], c + 2, any_nan);
-                        w[3] = fill_tail(a, q[u][3], c + 3, any_nan);
+                        w[0] = fill_tail(a, q[u][0], c, seen.any_nan);
+                        w[1] = fill_tail(a, q[u][1], c + 1, seen.any_nan);
+                        w[2] = fill_tail(a, q[u][2], c + 2, seen.any_nan);
+                        w[3] = fill_tail(a, q[u][3], c + 3, seen.any_nan);
                         if (yr) *reinterpret_cast<f4u*>(yr + c) = w;
                         *reinterpret_cast<float4*>(rowbuf + c) = make_float4(w[0], w[1], w[2], w[3]);
                     }
@@ -489,7 +557,7 @@ __global__ __launch_bounds__(THREADS) void operand_fill_block_kernel(FillArgs a)
             }
             if (tid < (K & 3)) {  // the last one to three cells
                 const int64_t c = 4 * n4 + tid;
-                const float v = fill_tail(a, xr[c], c, any_nan);
+                const float v = fill_tail(a, xr[c], c, seen.any_nan);
                 if (yr) yr[c] = v;
                 rowbuf[c] = v;
             }
@@ -515,14 +583,14 @@ __global__ __launch_bounds__(THREADS) void operand_fill_block_kernel(FillArgs a)
             if (vec && c0 >= K) continue;
             if (vec) {
                 float4 u = *reinterpret_cast<const float4*>(xr + c0), w = *reinterpret_cast<const float4*>(xr + c0 + 4);
-                u.x = fill_tail(a, u.x, c0, any_nan);
-                u.y = fill_tail(a, u.y, c0 + 1, any_nan);
-                u.z = fill_tail(a, u.z, c0 + 2, any_nan);
-                u.w = fill_tail(a, u.w, c0 + 3, any_nan);
-                w.x = fill_tail(a, w.x, c0 + 4, any_nan);
-                w.y = fill_tail(a, w.y, c0 + 5, any_nan);
-                w.z = fill_tail(a, w.z, c0 + 6, any_nan);
-                w.w = fill_tail(a, w.w, c0 + 7, any_nan);
+                u.x = fill_tail(a, u.x, c0, seen.any_nan);
+                u.y = fill_tail(a, u.y, c0 + 1, seen.any_nan);
+                u.z = fill_tail(a, u.z, c0 + 2, seen.any_nan);
+                u.w = fill_tail(a, u.w, c0 + 3, seen.any_nan);
+                w.x = fill_tail(a, w.x, c0 + 4, seen.any_nan);
+                w.y = fill_tail(a, w.y, c0 + 5, seen.any_nan);
+                w.z = fill_tail(a, w.z, c0 + 6, seen.any_nan);
+                w.w = fill_tail(a, w.w, c0 + 7, seen.any_nan);
                 if (yr) {
                     *reinterpret_cast<float4*>(yr + c0) = u;
                     *reinterpret_cast<float4*>(yr + c0 + 4) = w;
@@ -545,7 +613,7 @@ __global__ __launch_bounds__(THREADS) void operand_fill_block_kernel(FillArgs a)
                 for (int jj = 0; jj < 8; jj++) {
                     const int64_t c = c0 + jj;
                     if (c < K) {
-                        const float v = fill_tail(a, raw8[jj], c, any_nan);
+                        const float v = fill_tail(a, raw8[jj], c, seen.any_nan);
                         if (yr) yr[c] = v;
                         if (IN_LDS) rowbuf[c] = v;
                         s += v;
@@ -556,23 +624,10 @@ __global__ __launch_bounds__(THREADS) void operand_fill_block_kernel(FillArgs a)
             }
         }
         float mean = 0.f, sd = 1.f;
-        // pass 2 also counts how much of the row one value holds (its minimum, or — neighbouring cells equal — any value:
-        // operand_fill_kernel), which needs the row minimum of pass 1
+        // pass 2 also counts how much of the row one value holds (flag_mostly_one_value), which needs the row minimum of pass 1
         if (sizeof(T) != 4) {
-            vmin = -wave_max(-vmin);
-            vmax = wave_max(vmax);
-            if (lane == 0) red[wave] = vmin;
-            __syncthreads();
-            vmin = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
-#pragma unroll
-            for (int w = 4; w < WAVES; w++) vmin = fminf(vmin, red[w]);
-            __syncthreads();
-            if (lane == 0) red[wave] = vmax;
-            __syncthreads();
-            vmax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-#pragma unroll
-            for (int w = 4; w < WAVES; w++) vmax = fmaxf(vmax, red[w]);
-            __syncthreads();
+            vmin = -block_max(-vmin);
+            vmax = block_max(vmax);
         }
         float same = 0.f, adj = 0.f;
         auto count_repeats = [&](int64_t g, const float (&v)[8]) {
@@ -622,15 +677,9 @@ __global__ __launch_bounds__(THREADS) void operand_fill_block_kernel(FillArgs a)
         }
         float zmax2 = 0.f;
         if (sizeof(T) != 4) {
-            // the largest z^2 of the row sits at its largest or its smallest value: rounding is monotone, so these two
-            // evaluations are what the maximum over all cells was (NaN cells never counted; a row without a finite value: 0)
-            if (vmin <= vmax) {
-                const float z_lo = (vmin - mean) / sd, z_hi = (vmax - mean) / sd;
-                zmax2 = fmaxf(z_lo * z_lo, z_hi * z_hi);
-                if (!(zmax2 == zmax2)) zmax2 = 0.f;
-            }
+            zmax2 = zmax2_of_extremes(vmin, vmax, mean, sd);
             const float n_same = block_sum(same), n_adj = block_sum(adj);
-            if (n_same >= 0.85f * (float)K || n_adj >= 0.70f * (float)(K - 1)) coherent = true;
+            flag_mostly_one_value(n_same, n_adj, K, seen.coherent);
         }
         float sq = 0.f, m3 = 0.f, m4 = 0.f;
         for (int64_t g = tid; g < groups; g += THREADS) {
@@ -651,40 +700,34 @@ __global__ __launch_bounds__(THREADS) void operand_fill_block_kernel(FillArgs a)
                 }
             }
             if (sizeof(T) == 4) {
-                float* dst = reinterpret_cast<float*>(a.out) + (size_t)r * Kp + k0;
+                float* dst = reinterpret_cast<float*>(a.out) + (size_t)r * (a.kt * 32) + k0;
                 *reinterpret_cast<float4*>(dst) = make_float4(z[0], z[1], z[2], z[3]);
                 *reinterpret_cast<float4*>(dst + 4) = make_float4(z[4], z[5], z[6], z[7]);
             } else {
-                vec8<T> hi, lo;
+                halves<T, 8> hi, lo;
 #pragma unroll
                 for (int j = 0; j < 8; j++) {
                     const float zs = z[j] * a.out_scale;
-                    if (fabsf(zs) > 65504.f) overflow = true;
-                    const T hh = split_hi<T>(zs, k0 + j);
+                    if (fabsf(zs) > 65504.f) seen.overflow = true;
+                    const T hh = split_hi_flip<T>(zs, split_flip(k0 + j));
                     hi[j] = hh;
                     lo[j] = (T)(zs - (float)hh);
                 }
                 T* dst = reinterpret_cast<T*>(a.out) + ((size_t)r * a.kt + tile) * 64 + sub * 8;
-                *reinterpret_cast<vec8<T>*>(dst) = hi;
-                *reinterpret_cast<vec8<T>*>(dst + 32) = lo;
+                *reinterpret_cast<halves<T, 8>*>(dst) = hi;
+                *reinterpret_cast<halves<T, 8>*>(dst + 32) = lo;
             }
         }
         sq = block_sum(sq);  // its barriers also fence the LDS row against the next row's pass 1
         if (tid == 0) a.diag[r] = sq / (float)K;
         if (sizeof(T) != 4 && a.row_standardize) {
             const float s3 = block_sum(m3), s4 = block_sum(m4);
-            if (row_on_two_levels(sq / (float)K, s3 / (float)K, s4 / (float)K)) coherent = true;
+            if (row_on_two_levels(sq / (float)K, s3 / (float)K, s4 / (float)K)) seen.coherent = true;
         }
-        if (sizeof(T) != 4 && row_needs_fp32(zmax2, (float)K)) outlier = true;
+        if (sizeof(T) != 4 && row_needs_fp32(zmax2, (float)K)) seen.outlier = true;
     }
-    if (any_nan) atomicOr(&a.flags[1], 1u);
-    if (overflow) atomicOr(&a.flags[3], 1u);
-    if (outlier) atomicOr(&a.flags[4], 1u);
-    if (coherent) atomicOr(&a.flags[5], 1u);
+    seen.flush(a.flags);
 }
-
-template <typename T>
-using vec4h = T __attribute__((ext_vector_type(4)));
 
 // ---- round 5: ANY width up to VPT * 4 096 columns, the row in the registers of a sixteen-wave workgroup ------------------
 // The block kernel above parks a row in the LDS (or re-reads it from the L2) and walks it once per statistic, four waves a
@@ -712,7 +755,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS
     const int K = (int)a.cols, Kp = (int)a.kt * 32;
     const int n4p = Kp >> 2;  // pieces of the padded operand row
     const float kf = (float)K;
-    bool any_nan = false, overflow = false, outlier = false, coherent = false;
+    RowFlags seen;
     int phase = 0;
     // up to three sums (or maxima) over the workgroup with one barrier: the partials of consecutive calls alternate slots
     auto reduce3 = [&](float& p0, float& p1, float& p2, auto m0, auto m1, auto m2) {  // m*: std::true_type = maximum, false_type = sum
@@ -735,15 +778,12 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS
     };
     const std::true_type kMax;
     const std::false_type kSum;
-    // rounding direction of the hi half of each of this thread's VPT * 4 cells, one bit per cell (a hash of the COLUMN: the
-    // same for every row)
-    constexpr int DIRW = (VPT * 4 + 31) / 32;
-    uint32_t dir[DIRW] = {};
+    DirBits<VPT * 4> dir;  // this thread's cells: piece u, cell j -> bit 4 u + j
     if (sizeof(T) == 2) {
 #pragma unroll
         for (int u = 0; u < VPT; u++)
 #pragma unroll
-            for (int j = 0; j < 4; j++) dir[(u * 4 + j) >> 5] |= (split_flip(4 * (tid + THREADS * u) + j) >> 31) << ((u * 4 + j) & 31);
+            for (int j = 0; j < 4; j++) dir.set(u * 4 + j, 4 * (tid + THREADS * u) + j);
     }
     // Cells c .. c + 3 of a K-cell float vector WITHOUT a branch: hipcc answers a load inside a branch with s_waitcnt
     // vmcnt(0) right behind it — the four pieces of a row came in one after the other, each at full latency, and the
@@ -831,12 +871,9 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS
         asm volatile("" : "+s"(center_p), "+s"(recip_p));
         if (MODE >= 1 && !RESIDENT0) cs = cs_load(0);
         // (opaque per row: hoisted out of the row loop, the sixteen sign masks `dir` expands to cost sixteen registers)
-        uint32_t dir_r[DIRW];
+        DirBits<VPT * 4> dir_r = dir;
 #pragma unroll
-        for (int w = 0; w < DIRW; w++) {
-            dir_r[w] = dir[w];
-            asm volatile("" : "+v"(dir_r[w]));
-        }
+        for (uint32_t& w : dir_r.w) asm volatile("" : "+v"(w));
 #pragma unroll
         for (int u = 0; u < NP; u++) {
             const int c = 4 * (tid + THREADS * u);
@@ -873,7 +910,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS
                     // (no branch around a cell: the mixed piece computes every lane and SELECTS — a cell past the row is 0
                     // before and after; as `if (c + j < K) { ... }` each cell was an exec-mask region of its own)
                     const bool ok = !M(u) || c + j < K;
-                    if (M(u)) any_nan |= ok && t[j] != t[j];
+                    if (M(u)) seen.any_nan |= ok && t[j] != t[j];
                     if (MODE == 2) t[j] = skr_log2_of_sum1(__fadd_rn(t[j], a.shift));
                     v[u][j] = ok ? t[j] : 0.f;
                 }
@@ -912,7 +949,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS
         double rsd = 1.0;
         float same = 0.f, adj = 0.f;
         if (sizeof(T) != 4) {
-            // how much of the row one value holds: its minimum, or — neighbouring cells equal — any value (block kernel)
+            // how much of the row one value holds: its minimum, or — neighbouring cells equal — any value
 #pragma unroll
             for (int u = 0; u < NP; u++) {
                 const int c = 4 * (tid + THREADS * u);
@@ -961,12 +998,8 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS
         }
         float zmax2 = 0.f;
         if (sizeof(T) != 4) {
-            if (vmin <= vmax) {
-                const float z_lo = (vmin - mean) / sd, z_hi = (vmax - mean) / sd;
-                zmax2 = fmaxf(z_lo * z_lo, z_hi * z_hi);
-                if (!(zmax2 == zmax2)) zmax2 = 0.f;
-            }
-            if (same >= 0.85f * kf || adj >= 0.70f * (float)(K - 1)) coherent = true;
+            zmax2 = zmax2_of_extremes(vmin, vmax, mean, sd);
+            flag_mostly_one_value(same, adj, K, seen.coherent);
         }
         // ---- standardise, split, store (operand rows are zero-padded to whole 32-column tiles)
         float sq = 0.f, m3 = 0.f, m4 = 0.f;
@@ -980,40 +1013,28 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS
                 float t = v[u][j];  // (0 past the row)
                 if (a.row_standardize) t = !M(u) || k0 + j < K ? div_by_recip(__fsub_rn(t, mean), rsd) : 0.f;
                 z[j] = t;
-                sq = __fmaf_rn(t, t, sq);
-                if (sizeof(T) != 4) {
-                    const float t2 = t * t;
-                    m3 = fmaf(t2, t, m3);
-                    m4 = fmaf(t2, t2, m4);
-                }
+                add_moments<sizeof(T) != 4>(t, sq, m3, m4);
             }
-            if (sizeof(T) == 4) {
+            if constexpr (sizeof(T) == 4) {
                 float* dst = at(reinterpret_cast<float*>(a.out) + (size_t)r * Kp + 4 * THREADS * u, tb);
                 *reinterpret_cast<float4*>(dst) = make_float4(z[0], z[1], z[2], z[3]);
             } else {
-                vec4h<T> hi, lo;
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const float zs = z[j] * a.out_scale;
-                    if (fabsf(zs) > 65504.f) overflow = true;
-                    const T hh = split_hi_flip<T>(zs, (dir_r[(u * 4 + j) >> 5] << (31 - ((u * 4 + j) & 31))) & 0x80000000u);
-                    hi[j] = hh;
-                    lo[j] = (T)(zs - (float)hh);
-                }
+                halves<T, 4> hi, lo;
+                if (split_cells<T, 4>(z, a.out_scale, [&](int j) __attribute__((always_inline)) { return dir_r.flip(u * 4 + j); }, hi, lo)) seen.overflow = true;
                 // piece i = tid + THREADS u sits in tile i / 8, columns 4 (i % 8): (tid / 8) tiles + THREADS / 8 tiles a piece
                 T* dst = at(reinterpret_cast<T*>(a.out) + ((size_t)r * a.kt + (THREADS / 8) * u) * 64,
                             (uint32_t)(((tid >> 3) * 64 + 4 * (tid & 7)) * sizeof(T)));
-                *reinterpret_cast<vec4h<T>*>(dst) = hi;
-                *reinterpret_cast<vec4h<T>*>(dst + 32) = lo;
+                *reinterpret_cast<halves<T, 4>*>(dst) = hi;
+                *reinterpret_cast<halves<T, 4>*>(dst + 32) = lo;
             }
             __builtin_amdgcn_sched_barrier(0);  // one piece at a time: interleaved, the splits of all pieces are alive at once
         }
         reduce3(sq, m3, m4, kSum, kSum, kSum);
         if (tid == 0) a.diag[r] = sq / kf;
-        if (sizeof(T) != 4 && a.row_standardize && row_on_two_levels(sq / kf, m3 / kf, m4 / kf)) coherent = true;
-        if (sizeof(T) != 4 && row_needs_fp32(zmax2, kf)) outlier = true;
+        if (sizeof(T) != 4 && a.row_standardize && row_on_two_levels(sq / kf, m3 / kf, m4 / kf)) seen.coherent = true;
+        if (sizeof(T) != 4 && row_needs_fp32(zmax2, kf)) seen.outlier = true;
     }
-    if (nan_lanes) any_nan = true;
+    if (nan_lanes) seen.any_nan = true;
     };
     // which body this wave runs: pieces [0, whole) are whole in every lane of the wave; piece `whole` is either entirely past
     // the padded row (then so are the ones behind it) or MIXED — the ragged piece, the operand's zero padding, lanes past it
@@ -1036,10 +1057,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS
     else if (whole == 2 && !mixed) run(std::integral_constant<int, 2>(), std::false_type());
     else if (whole == 2) run(std::integral_constant<int, 3>(), std::true_type());
     else __builtin_trap();
-    if (any_nan) atomicOr(&a.flags[1], 1u);
-    if (overflow) atomicOr(&a.flags[3], 1u);
-    if (outlier) atomicOr(&a.flags[4], 1u);
-    if (coherent) atomicOr(&a.flags[5], 1u);
+    seen.flush(a.flags);
 }
 
 // Register-resident variant for K = VPL * 256 columns (k = 5: VPL 4, k = 6: VPL 16): a wave keeps
@@ -1068,6 +1086,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VPL == 16 ?
     // base in scalar registers (derived from threadIdx it is 'divergent', and all addresses become 64-bit VGPR pairs)
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), waves = blockDim.x >> 6;
     constexpr int64_t K = (int64_t)VPL * 256 * RW;
+    // (its own bools, handed to RowFlags at the end: with the struct alive through the row the five f16f8 instantiations for
+    // 4^7 columns spill 24 - 28 bytes more)
     bool any_nan = false, overflow = false, outlier = false, coherent = false, repeats = false;
     // sum / max over the row; `slot` separates the reductions of one row so that one barrier each is enough
     auto row_sum = [&](float v, int slot) -> float {
@@ -1086,14 +1106,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VPL == 16 ?
     };
     const int64_t r_first = RW == 1 ? (int64_t)blockIdx.x * waves + wave : (int64_t)blockIdx.x;
     const int piece0 = RW == 1 ? 0 : wave;  // first 256-column piece of this wave
-    // rounding direction of the hi half of each of this lane's VPL * 4 cells, one bit per cell (the same for every row)
-    uint32_t dir[(VPL * 4 + 31) / 32] = {};
+    DirBits<VPL * 4> dir;  // this lane's cells: piece i, cell j -> bit 4 i + j
     if (sizeof(T) == 2) {
 #pragma unroll
         for (int i = 0; i < VPL; i++)
 #pragma unroll
-            for (int j = 0; j < 4; j++)
-                dir[(i * 4 + j) >> 5] |= (split_flip((int64_t)(i * RW + piece0) * 256 + lane * 4 + j) >> 31) << ((i * 4 + j) & 31);
+            for (int j = 0; j < 4; j++) dir.set(i * 4 + j, (int64_t)(i * RW + piece0) * 256 + lane * 4 + j);
     }
     // launched with exactly one row per wave (RW == 1) or per workgroup (RW == 4), see launch_fill: no row loop
     const int64_t r = r_first;
@@ -1209,11 +1227,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VPL == 16 ?
                 zmax = fmaxf(fmaxf(zmax, fmaxf(fabsf(v[i].x), fabsf(v[i].y))), fmaxf(fabsf(v[i].z), fabsf(v[i].w)));
             zmax = row_max(zmax, 4);
             if (row_needs_fp32(zmax * zmax, (float)K)) outlier = true;
+            // (the fp16 range is tested once per row, on the largest |z|, not per cell in split_cells)
             if (zmax * a.out_scale > 65504.f) overflow = true;
-            // Share of the row held by one repeated value — for count data its minimum, the empty bins.  Near-copies
-            // of such a row have only positive products, small ones added to a sum that is already large, and the
-            // truncating accumulate then loses up to an ulp of the sum per add (tools/margin_probe.py: the bar is
-            // reached at 97 %); the contraction restarts its accumulators twice as often for flagged operands.
+            // share of the row held by one repeated value, its minimum or any other (flag_mostly_one_value; here with the
+            // equal pairs inside a lane's groups of four cells: kEqualPairShareInQuads)
             float zmin = v[0].x;
 #pragma unroll
             for (int i = 0; i < VPL; i++) zmin = fminf(fminf(zmin, fminf(v[i].x, v[i].y)), fminf(v[i].z, v[i].w));
@@ -1222,14 +1239,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VPL == 16 ?
 #pragma unroll
             for (int i = 0; i < VPL; i++)
                 same += (float)((v[i].x == zmin) + (v[i].y == zmin) + (v[i].z == zmin) + (v[i].w == zmin));
-            if (row_sum(same, 6) >= 0.85f * (float)K) coherent = true;
-            // ... or by any one value, which need not be the minimum (operand_fill_kernel): of the three neighbouring pairs
-            // inside each group of four cells a lane holds, 85 % of one value leaves at least 0.45 K equal
+            if (row_sum(same, 6) >= kOneValueShare * (float)K) coherent = true;
             float eq = 0.f;
 #pragma unroll
             for (int i = 0; i < VPL; i++) eq += (float)((v[i].x == v[i].y) + (v[i].y == v[i].z) + (v[i].z == v[i].w));
             eq = row_sum(eq, 7);
-            if (eq >= 0.45f * (float)K) coherent = true;
+            if (eq >= kEqualPairShareInQuads * (float)K) coherent = true;
             if (X8 && eq >= (float)K * (1.0f / 256.0f)) repeats = true;
             if constexpr (X8) {
                 // ... and rows that repeat values WITHOUT neighbours being equal (a periodic row against a shifted copy
@@ -1273,21 +1288,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VPL == 16 ?
                 *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.out) + (size_t)r * K + c) = v[i];
             } else {
                 const float z[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
-                vec4h<T> hi, lo;
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const float zs = z[j] * a.out_scale;
-                    // X8: hi rounded to NEAREST — the hashed direction exists for rows of one repeated value, which never keep
-                    // this layout, and it doubles |lo| (rms 0.58 instead of 0.29 ulp), i.e. the cross term the fp8 copies carry
-                    const T hh = X8 ? (T)zs : split_hi_flip<T>(zs, (dir[(i * 4 + j) >> 5] << (31 - ((i * 4 + j) & 31))) & 0x80000000u);
-                    hi[j] = hh;
-                    lo[j] = (T)(zs - (float)hh);
-                }
+                halves<T, 4> hi, lo;
+                // X8: hi rounded to NEAREST — the hashed direction exists for rows of one repeated value, which never keep
+                // this layout, and it doubles |lo| (rms 0.58 instead of 0.29 ulp), i.e. the cross term the fp8 copies carry
+                if constexpr (X8) split_cells<T, 4>(z, a.out_scale, SplitNearest(), hi, lo);
+                else split_cells<T, 4>(z, a.out_scale, [&](int j) __attribute__((always_inline)) { return dir.flip(i * 4 + j); }, hi, lo);
                 if constexpr (X8) {
                     // line 2d: 64 fp16 hi halves of columns 64d .. 64d+63; line 2d+1: their fp8 copies hi / 128, then lo x 16
                     char* line = reinterpret_cast<char*>(a.out) + ((size_t)r * a.kt + 2 * (size_t)(c >> 6)) * 128;
                     const int j = (int)(c & 63);
-                    *reinterpret_cast<vec4h<T>*>(line + 2 * j) = hi;
+                    *reinterpret_cast<halves<T, 4>*>(line + 2 * j) = hi;
                     int h8 = 0, l8 = 0;
                     h8 = __builtin_amdgcn_cvt_pk_fp8_f32((float)hi[0] * 0x1.0p-7f, (float)hi[1] * 0x1.0p-7f, h8, false);
                     h8 = __builtin_amdgcn_cvt_pk_fp8_f32((float)hi[2] * 0x1.0p-7f, (float)hi[3] * 0x1.0p-7f, h8, true);
@@ -1311,8 +1321,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VPL == 16 ?
                     }
                 } else {
                     T* dst = reinterpret_cast<T*>(a.out) + ((size_t)r * a.kt + (c >> 5)) * 64 + (c & 31);
-                    *reinterpret_cast<vec4h<T>*>(dst) = hi;
-                    *reinterpret_cast<vec4h<T>*>(dst + 32) = lo;
+                    *reinterpret_cast<halves<T, 4>*>(dst) = hi;
+                    *reinterpret_cast<halves<T, 4>*>(dst + 32) = lo;
                 }
                 if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0);
             }
@@ -1341,11 +1351,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VPL == 16 ?
             }
         }
     }
-    if (any_nan) atomicOr(&a.flags[1], 1u);
-    if (overflow) atomicOr(&a.flags[3], 1u);
-    if (outlier) atomicOr(&a.flags[4], 1u);
-    if (coherent) atomicOr(&a.flags[5], 1u);
-    if (repeats) atomicOr(&a.flags[6], 1u);
+    RowFlags{any_nan, overflow, outlier, coherent, repeats}.flush(a.flags);
 }
 
 // r[i, i] of a self-comparison = <z_i, z_i> / K.  The contraction adds 4 096 squares into one float32
@@ -1389,9 +1395,49 @@ bool is_f32_precision(int p) {
     return p == SKR_PREC_FP32 || p == SKR_PREC_BF16X3 || p == SKR_PREC_F16X3 || p == SKR_PREC_F16F8;
 }
 
+// ---- which instantiation a launch takes, as compile-time constants handed to a generic lambda
+template <class T>
+struct type_c {
+    using type = T;
+};
+// storage kind of the operand -> (element type, X8): 0 float32, 1 bf16 halves, 2 fp16 halves, 3 the H / X lines of f16f8
+// (written by the register kernels alone: every other kernel sees plain fp16 halves)
+template <class F>
+int with_kind(int kind, F f) {
+    if (kind == 0) return f(type_c<float>(), std::false_type());
+    if (kind == 1) return f(type_c<__bf16>(), std::false_type());
+    if (kind == 3) return f(type_c<_Float16>(), std::true_type());
+    return f(type_c<_Float16>(), std::false_type());
+}
+// the register kernels' (MODE, HASY): rows as they are (never with y), float32 centre + scale, + the Log2.post tail
+template <class F>
+int with_mode(int reg_mode, bool has_y, F f) {
+    if (reg_mode == 0) return f(std::integral_constant<int, 0>(), std::false_type());
+    if (reg_mode == 1 && has_y) return f(std::integral_constant<int, 1>(), std::true_type());
+    if (reg_mode == 1) return f(std::integral_constant<int, 1>(), std::false_type());
+    if (has_y) return f(std::integral_constant<int, 2>(), std::true_type());
+    return f(std::integral_constant<int, 2>(), std::false_type());
+}
+
+// a.scale_recip: float64 reciprocals of the float32 scale vector, made once per launch — a quotient then costs 3
+// instructions (div_by_recip)
+int make_scale_recip(skr_ctx* ctx, FillArgs& a) {
+    if (ctx->d_recip_len < (size_t)a.cols) {
+        if (ctx->d_recip) SKR_HIP(hipFree(ctx->d_recip));
+        ctx->d_recip = nullptr;
+        ctx->d_recip_len = 0;
+        SKR_HIP(hipMalloc((void**)&ctx->d_recip, (size_t)a.cols * sizeof(double)));
+        ctx->d_recip_len = (size_t)a.cols;
+    }
+    hipLaunchKernelGGL(recip64_kernel, dim3((unsigned)((a.cols + 255) / 256)), dim3(256), 0, ctx->stream,
+                       reinterpret_cast<const float*>(a.scale), ctx->d_recip, a.cols);
+    a.scale_recip = ctx->d_recip;
+    return SKR_OK;
+}
+
 // launches the fill kernel that suits the row width and the operand's storage kind
 int launch_fill(skr_ctx* ctx, const skr_operand* op, const FillArgs& a_in) {
-    const FillArgs& a = a_in;
+    FillArgs a = a_in;
     const size_t row_floats = (size_t)((a.cols + 3) & ~(int64_t)3);
     const bool wide = row_floats * 4 > 150 * 1024;  // k >= 8: the row does not fit the LDS
     const int waves = (int)std::max<size_t>(1, std::min<size_t>(4, (64 * 1024) / (row_floats * 4)));
@@ -1405,19 +1451,7 @@ int launch_fill(skr_ctx* ctx, const skr_operand* op, const FillArgs& a_in) {
     if (a.ck == 0 && a.sk == 0 && !a.post && !a.y) reg_mode = 0;
     else if (a.ck == 1 && a.sk == 1) reg_mode = a.post ? 2 : 1;
     if ((a.cols == 16384 || a.cols == 4096 || a.cols == 1024) && reg_mode >= 0) {
-        FillArgs a = a_in;
-        if (reg_mode >= 1) {  // float64 reciprocals of the scale vector: a quotient then costs 3 instructions (div_by_recip)
-            if (ctx->d_recip_len < (size_t)a.cols) {
-                if (ctx->d_recip) SKR_HIP(hipFree(ctx->d_recip));
-                ctx->d_recip = nullptr;
-                ctx->d_recip_len = 0;
-                SKR_HIP(hipMalloc((void**)&ctx->d_recip, (size_t)a.cols * sizeof(double)));
-                ctx->d_recip_len = (size_t)a.cols;
-            }
-            hipLaunchKernelGGL(recip64_kernel, dim3((unsigned)((a.cols + 255) / 256)), dim3(256), 0, ctx->stream,
-                               reinterpret_cast<const float*>(a.scale), ctx->d_recip, a.cols);
-            a.scale_recip = ctx->d_recip;
-        }
+        if (reg_mode >= 1) SKR_TRY(make_scale_recip(ctx, a));
         const int64_t rows_per_wg = a.cols == 16384 ? 1 : 4;
         // One row per wave (k <= 6: four rows per workgroup) or per workgroup (k = 7), the workgroups dispatched in order:
         // the rows being read and written form a compact front (0.69 -> 0.63 ms at 50 000 x 4 096 against a persistent
@@ -1428,95 +1462,49 @@ int launch_fill(skr_ctx* ctx, const skr_operand* op, const FillArgs& a_in) {
         SKR_REQUIRE(all_wgs <= 0x7fffffff, "too many rows for one fill launch (%lld)", (long long)a.rows);
         const unsigned rgrid = (unsigned)std::max<int64_t>(1, all_wgs);
         SkrProfScope prof(ctx, "operand_fill");
-#define LAUNCH_REG2(T, V, RW, X)                                                                                           \
-    do {                                                                                                                   \
-        if (reg_mode == 0) hipLaunchKernelGGL((operand_fill_reg_kernel<T, V, 0, RW, false, X>), dim3(rgrid), dim3(256), 0, ctx->stream, a);      \
-        else if (reg_mode == 1 && a.y) hipLaunchKernelGGL((operand_fill_reg_kernel<T, V, 1, RW, true, X>), dim3(rgrid), dim3(256), 0, ctx->stream, a); \
-        else if (reg_mode == 1) hipLaunchKernelGGL((operand_fill_reg_kernel<T, V, 1, RW, false, X>), dim3(rgrid), dim3(256), 0, ctx->stream, a); \
-        else if (a.y) hipLaunchKernelGGL((operand_fill_reg_kernel<T, V, 2, RW, true, X>), dim3(rgrid), dim3(256), 0, ctx->stream, a);             \
-        else hipLaunchKernelGGL((operand_fill_reg_kernel<T, V, 2, RW, false, X>), dim3(rgrid), dim3(256), 0, ctx->stream, a);                    \
-    } while (0)
-#define LAUNCH_REG(T, X)                                  \
-    do {                                                  \
-        if (a.cols == 16384) LAUNCH_REG2(T, 16, 4, X);    \
-        else if (a.cols == 4096) LAUNCH_REG2(T, 16, 1, X); \
-        else LAUNCH_REG2(T, 4, 1, X);                      \
-    } while (0)
-        if (op->kind == 0) LAUNCH_REG(float, false);
-        else if (op->kind == 1) LAUNCH_REG(__bf16, false);
-        else if (op->kind == 3) LAUNCH_REG(_Float16, true);
-        else LAUNCH_REG(_Float16, false);
-#undef LAUNCH_REG
-#undef LAUNCH_REG2
+        auto with_width = [&](auto f) -> int {  // (VPL, RW)
+            if (a.cols == 16384) return f(std::integral_constant<int, 16>(), std::integral_constant<int, 4>());
+            if (a.cols == 4096) return f(std::integral_constant<int, 16>(), std::integral_constant<int, 1>());
+            return f(std::integral_constant<int, 4>(), std::integral_constant<int, 1>());
+        };
+        with_kind(op->kind, [&](auto t, auto x8) -> int {
+            return with_width([&](auto vpl, auto rw) -> int {
+                return with_mode(reg_mode, a.y != nullptr, [&](auto mode, auto hasy) -> int {
+                    using T = typename decltype(t)::type;
+                    hipLaunchKernelGGL((operand_fill_reg_kernel<T, decltype(vpl)::value, decltype(mode)::value, decltype(rw)::value, decltype(hasy)::value, decltype(x8)::value>), dim3(rgrid), dim3(256), 0, ctx->stream, a);
+                    return SKR_OK;
+                });
+            });
+        });
         SKR_HIP(hipGetLastError());
-    } else if (reg_mode >= 0 && op->kind != 3 && a.cols > 8192 && a.cols <= 16384) {
-        // round 5: ANY width of 8 193 .. 16 384 columns but 4^7 (5^6, 10^4, 22^3 ...) — the row in the registers of a
-        // sixteen-wave workgroup (operand_fill_rowreg_kernel; multiples of 8 too: the block kernel below takes 3.1 ms where
-        // this one takes 1.8 on 50 000 x 15 632); widths below stay with the wave-per-row kernel and its numpy-ordered
-        // sums, everything else with the block kernel (a 65 536-cell row in registers, 64 per thread, spills: measured)
-        FillArgs a = a_in;
-        if (reg_mode >= 1) {  // float64 reciprocals of the scale vector (as for the register kernels above)
-            if (ctx->d_recip_len < (size_t)a.cols) {
-                if (ctx->d_recip) SKR_HIP(hipFree(ctx->d_recip));
-                ctx->d_recip = nullptr;
-                ctx->d_recip_len = 0;
-                SKR_HIP(hipMalloc((void**)&ctx->d_recip, (size_t)a.cols * sizeof(double)));
-                ctx->d_recip_len = (size_t)a.cols;
-            }
-            hipLaunchKernelGGL(recip64_kernel, dim3((unsigned)((a.cols + 255) / 256)), dim3(256), 0, ctx->stream,
-                               reinterpret_cast<const float*>(a.scale), ctx->d_recip, a.cols);
-            a.scale_recip = ctx->d_recip;
-        }
-        SkrProfScope prof(ctx, "operand_fill");
-        // one sixteen-wave workgroup per CU (128 registers a thread) that prefetches its next row; two eight-wave workgroups
-        // per CU without prefetch were slower (4.18 against 3.47 ms: profiles/r5_generic_width_arms.log)
-        const unsigned rgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(a.rows, (int64_t)ctx->num_cu));
-#define LAUNCH_ROWREG(T)                                                                                                    \
-    do {                                                                                                                    \
-        if (reg_mode == 0) hipLaunchKernelGGL((operand_fill_rowreg_kernel<T, 4, 0, false, 1024>), dim3(rgrid), dim3(1024), 0, ctx->stream, a);      \
-        else if (reg_mode == 1 && a.y) hipLaunchKernelGGL((operand_fill_rowreg_kernel<T, 4, 1, true, 1024>), dim3(rgrid), dim3(1024), 0, ctx->stream, a); \
-        else if (reg_mode == 1) hipLaunchKernelGGL((operand_fill_rowreg_kernel<T, 4, 1, false, 1024>), dim3(rgrid), dim3(1024), 0, ctx->stream, a); \
-        else if (a.y) hipLaunchKernelGGL((operand_fill_rowreg_kernel<T, 4, 2, true, 1024>), dim3(rgrid), dim3(1024), 0, ctx->stream, a);             \
-        else hipLaunchKernelGGL((operand_fill_rowreg_kernel<T, 4, 2, false, 1024>), dim3(rgrid), dim3(1024), 0, ctx->stream, a);                    \
-    } while (0)
-        if (op->kind == 0) LAUNCH_ROWREG(float);
-        else if (op->kind == 1) LAUNCH_ROWREG(__bf16);
-        else LAUNCH_ROWREG(_Float16);
-#undef LAUNCH_ROWREG
-        SKR_HIP(hipGetLastError());
-    } else if (reg_mode >= 0 && op->kind != 3 && a.cols == 65536) {
-        // round 5: 4^8 columns — the same kernel with sixteen pieces (64 cells) a thread and no second row in flight: ONE read
-        // of the 256 KB row instead of the block kernel's four (its passes re-read the row through an L2 that 256 rows in
-        // flight overflow), 8.84 -> 3.79 ms per 20 000 rows in the pipeline form, 9.3 -> 2.3 bare.  Every piece of every
-        // wave is whole at this width; other widths above 16 384 would need the mixed-piece bodies for up to sixteen
-        // pieces and stay with the block kernel.
-        FillArgs a = a_in;
-        if (reg_mode >= 1) {
-            if (ctx->d_recip_len < (size_t)a.cols) {
-                if (ctx->d_recip) SKR_HIP(hipFree(ctx->d_recip));
-                ctx->d_recip = nullptr;
-                ctx->d_recip_len = 0;
-                SKR_HIP(hipMalloc((void**)&ctx->d_recip, (size_t)a.cols * sizeof(double)));
-                ctx->d_recip_len = (size_t)a.cols;
-            }
-            hipLaunchKernelGGL(recip64_kernel, dim3((unsigned)((a.cols + 255) / 256)), dim3(256), 0, ctx->stream,
-                               reinterpret_cast<const float*>(a.scale), ctx->d_recip, a.cols);
-            a.scale_recip = ctx->d_recip;
-        }
+    } else if (reg_mode >= 0 && op->kind != 3 && ((a.cols > 8192 && a.cols <= 16384) || a.cols == 65536)) {
+        // The row in the registers of a sixteen-wave workgroup (operand_fill_rowreg_kernel), at two kinds of width.
+        // 8 193 .. 16 384 columns but 4^7 (round 5: 5^6, 10^4, 22^3 ...), 4 pieces a thread — multiples of 8 too: the block
+        // kernel below takes 3.1 ms where this one takes 1.8 on 50 000 x 15 632.  Widths below stay with the wave-per-row
+        // kernel and its numpy-ordered sums.  One sixteen-wave workgroup per CU (128 registers a thread) that prefetches its
+        // next row; two eight-wave workgroups per CU without prefetch were slower (4.18 against 3.47 ms:
+        // profiles/r5_generic_width_arms.log).
+        // 4^8 columns (round 5), sixteen pieces (64 cells) a thread and NO second row in flight (prefetching one on top of
+        // the 64 cells spills: measured): ONE read of the 256 KB row instead of the block kernel's four (its passes re-read
+        // the row through an L2 that 256 rows in flight overflow), 8.84 -> 3.79 ms per 20 000 rows in the pipeline form,
+        // 9.3 -> 2.3 bare.  Every piece of every wave is whole at this width; other widths above 16 384 would need the
+        // mixed-piece bodies for up to sixteen pieces and stay with the block kernel.
+        if (reg_mode >= 1) SKR_TRY(make_scale_recip(ctx, a));
         SkrProfScope prof(ctx, "operand_fill");
         const unsigned rgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(a.rows, (int64_t)ctx->num_cu));
-#define LAUNCH_ROWREG16(T)                                                                                                  \
-    do {                                                                                                                    \
-        if (reg_mode == 0) hipLaunchKernelGGL((operand_fill_rowreg_kernel<T, 16, 0, false, 1024>), dim3(rgrid), dim3(1024), 0, ctx->stream, a);      \
-        else if (reg_mode == 1 && a.y) hipLaunchKernelGGL((operand_fill_rowreg_kernel<T, 16, 1, true, 1024>), dim3(rgrid), dim3(1024), 0, ctx->stream, a); \
-        else if (reg_mode == 1) hipLaunchKernelGGL((operand_fill_rowreg_kernel<T, 16, 1, false, 1024>), dim3(rgrid), dim3(1024), 0, ctx->stream, a); \
-        else if (a.y) hipLaunchKernelGGL((operand_fill_rowreg_kernel<T, 16, 2, true, 1024>), dim3(rgrid), dim3(1024), 0, ctx->stream, a);             \
-        else hipLaunchKernelGGL((operand_fill_rowreg_kernel<T, 16, 2, false, 1024>), dim3(rgrid), dim3(1024), 0, ctx->stream, a);                    \
-    } while (0)
-        if (op->kind == 0) LAUNCH_ROWREG16(float);
-        else if (op->kind == 1) LAUNCH_ROWREG16(__bf16);
-        else LAUNCH_ROWREG16(_Float16);
-#undef LAUNCH_ROWREG16
+        auto with_pieces = [&](auto f) -> int {  // VPT: 16-byte pieces of the row per thread
+            if (a.cols == 65536) return f(std::integral_constant<int, 16>());
+            return f(std::integral_constant<int, 4>());
+        };
+        with_kind(op->kind, [&](auto t, auto) -> int {
+            return with_pieces([&](auto vpt) -> int {
+                return with_mode(reg_mode, a.y != nullptr, [&](auto mode, auto hasy) -> int {
+                    using T = typename decltype(t)::type;
+                    hipLaunchKernelGGL((operand_fill_rowreg_kernel<T, decltype(vpt)::value, decltype(mode)::value, decltype(hasy)::value, 1024>), dim3(rgrid), dim3(1024), 0, ctx->stream, a);
+                    return SKR_OK;
+                });
+            });
+        });
         SKR_HIP(hipGetLastError());
     } else if (row_floats * 4 >= 32 * 1024) {  // k >= 7: one workgroup per row
         SkrProfScope prof(ctx, "operand_fill");
@@ -1525,22 +1513,18 @@ int launch_fill(skr_ctx* ctx, const skr_operand* op, const FillArgs& a_in) {
         const unsigned wgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(a.rows, (int64_t)ctx->num_cu * bper_cu));
         // sixteen-wave workgroups: two per CU at most (2 048 threads), one when the row takes more than half the LDS
         const unsigned wgrid16 = (unsigned)std::max<int64_t>(1, std::min<int64_t>(a.rows, (int64_t)ctx->num_cu * std::min<int64_t>(2, bper_cu)));
-#define LAUNCH_BLOCK(T)                                                                                           \
-    do {                                                                                                          \
-        if (wide) {                                                                                               \
-            hipLaunchKernelGGL((operand_fill_block_kernel<T, false, 1024>), dim3(wgrid16), dim3(1024), 0, ctx->stream, a); \
-        } else {                                                                                                  \
-            SKR_TRY(skr_kernel_lds(ctx, reinterpret_cast<const void*>(operand_fill_block_kernel<T, true>), blds)); \
-            hipLaunchKernelGGL((operand_fill_block_kernel<T, true>), dim3(wgrid), dim3(256), blds, ctx->stream, a); \
-        }                                                                                                         \
-    } while (0)
-        if (op->kind == 0) LAUNCH_BLOCK(float);
-        else if (op->kind == 1) LAUNCH_BLOCK(__bf16);
-        else LAUNCH_BLOCK(_Float16);
-#undef LAUNCH_BLOCK
+        SKR_TRY(with_kind(op->kind, [&](auto t, auto) -> int {
+            using T = typename decltype(t)::type;
+            if (wide) {
+                hipLaunchKernelGGL((operand_fill_block_kernel<T, false, 1024>), dim3(wgrid16), dim3(1024), 0, ctx->stream, a);
+            } else {
+                SKR_TRY(skr_kernel_lds(ctx, reinterpret_cast<const void*>(operand_fill_block_kernel<T, true>), blds));
+                hipLaunchKernelGGL((operand_fill_block_kernel<T, true>), dim3(wgrid), dim3(256), blds, ctx->stream, a);
+            }
+            return SKR_OK;
+        }));
         SKR_HIP(hipGetLastError());
     } else {
-        FillArgs a = a_in;
         a.np_plan = nullptr;
         if (a.row_standardize && a.cols <= kNpExactMaxCols) {
             // rows summed in numpy's pairwise order: the recursion for this width, unrolled here once and kept on the device
@@ -1556,18 +1540,29 @@ int launch_fill(skr_ctx* ctx, const skr_operand* op, const FillArgs& a_in) {
             a.np_plan = reinterpret_cast<const NpPlan*>(ctx->d_np_plan);
         }
         SkrProfScope prof(ctx, "operand_fill");
-#define LAUNCH(T)                                                                                         \
-    do {                                                                                                      \
-        SKR_TRY(skr_kernel_lds(ctx, reinterpret_cast<const void*>(operand_fill_kernel<T>), lds));             \
-        hipLaunchKernelGGL(operand_fill_kernel<T>, dim3(grid), dim3(64 * waves), lds, ctx->stream, a);               \
-    } while (0)
-        if (op->kind == 0) LAUNCH(float);
-        else if (op->kind == 1) LAUNCH(__bf16);
-        else LAUNCH(_Float16);
-#undef LAUNCH
+        SKR_TRY(with_kind(op->kind, [&](auto t, auto) -> int {
+            using T = typename decltype(t)::type;
+            SKR_TRY(skr_kernel_lds(ctx, reinterpret_cast<const void*>(operand_fill_kernel<T>), lds));
+            hipLaunchKernelGGL(operand_fill_kernel<T>, dim3(grid), dim3(64 * waves), lds, ctx->stream, a);
+            return SKR_OK;
+        }));
         SKR_HIP(hipGetLastError());
     }
     return SKR_OK;
+}
+
+// the arguments of a second fill of the same rows into another layout: the normalised counts, if they were asked for,
+// are already in y — refill from them as they are
+FillArgs refill_args(const FillArgs& a) {
+    FillArgs b = a;
+    if (a.y) {
+        b.x = a.y;
+        b.y = nullptr;
+        b.ck = b.sk = 0;
+        b.center = b.scale = nullptr;
+        b.post = 0;
+    }
+    return b;
 }
 
 }  // namespace
@@ -1749,19 +1744,11 @@ extern "C" int skr_operand_fill(skr_ctx* ctx, const skr_mat* x, const skr_mat* c
         }
         if (split && ctx->h_flags[4] != 0) {
             // a row is dominated by so few columns that the split contraction would drop the others
-            // (see row_needs_fp32): same storage, float32 layout, and the fp32 kernel from here on.  The
-            // normalised counts, if they were asked for, are already in y: refill from them as they are.
+            // (see row_needs_fp32): same storage, float32 layout, and the fp32 kernel from here on
             op->kind = 0;
             op->scale = 1.f;
-            FillArgs b = a;
+            FillArgs b = refill_args(a);
             b.out_scale = 1.f;
-            if (a.y) {
-                b.x = a.y;
-                b.y = nullptr;
-                b.ck = b.sk = 0;
-                b.center = b.scale = nullptr;
-                b.post = 0;
-            }
             SKR_TRY(launch_fill(ctx, op, b));
             return SKR_OK;
         }
@@ -1775,14 +1762,7 @@ extern "C" int skr_operand_fill(skr_ctx* ctx, const skr_mat* x, const skr_mat* c
             op->kind = 2;
             op->precision = SKR_PREC_F16X3;
             op->x8_routed_back = true;
-            FillArgs b = a;
-            if (a.y) {  // the normalised counts are already in y: refill from them as they are
-                b.x = a.y;
-                b.y = nullptr;
-                b.ck = b.sk = 0;
-                b.center = b.scale = nullptr;
-                b.post = 0;
-            }
+            const FillArgs b = refill_args(a);
             SKR_HIP(hipMemsetAsync(ctx->d_flags + 5, 0, 4, ctx->stream));
             SKR_TRY(launch_fill(ctx, op, b));
             SKR_HIP(hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));

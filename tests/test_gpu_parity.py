@@ -654,12 +654,16 @@ def test_fill_quotients_are_the_ieee_quotients(cols, L, ctx):
     assert nan.mean() > 0.005 and (np.abs(want[~nan]) < 1.2e-38).mean() > 0.05   # NaNs and subnormal / zero quotients occurred
 
 
-@pytest.mark.parametrize("cols", [256, 4096, 16384])
+@pytest.mark.parametrize("cols", [256, 4096, 16384, 8200, 9999, 16807, 40004, 65536])
 def test_split_halves_against_a_numpy_restatement(cols, L, ctx):
     """The stored fp16 halves, bit for bit: hi = z x scale rounded DOWN or UP by the hash of the column (operand.hip:
     split_hi_f16 — one conversion and a step, not the device library's directed conversions), lo = fp16(z x scale - hi).
-    Restated with numpy's float16 conversion and nextafter; the three widths take the three fill kernels (wave-private
-    LDS rows, one row per wave in registers, four waves per row)."""
+    Restated with numpy's float16 conversion and nextafter; the widths take every place the fill kernels split a row:
+    wave-private LDS rows (256), one row per wave in registers (4 096), four waves per row
+    (16 384), the row in the registers of sixteen waves with 4 pieces a thread (8 200; 9 999: ragged last piece) and with
+    16 (65 536), a workgroup per row with the row in the LDS (16 807, ragged) and re-read from global memory by 1 024
+    threads (40 004).  The register-resident kernels split through split_cells, the wave-per-row and the workgroup-per-row
+    kernel write their pass 3 out.  The columns that pad the last 32-column tile hold +0 in both halves."""
     rng = np.random.default_rng(cols)
     rows = 64
     scale = np.float32(2.0 ** np.floor(np.log2(32768.0 / np.sqrt(cols))))
@@ -680,8 +684,9 @@ def test_split_halves_against_a_numpy_restatement(cols, L, ctx):
         h_dn = np.where(back > zs, np.nextafter(h, np.float16(-np.inf)), h)
         hi = np.where(up, h_up, h_dn).astype(np.float16)
         lo = (zs - hi.astype(np.float32)).astype(np.float16)
-    want_hi = hi.view(np.uint16).reshape(rows, kt, 32)
-    want_lo = lo.view(np.uint16).reshape(rows, kt, 32)
+    pad = np.zeros((rows, kt * 32 - cols), np.uint16)  # +0
+    want_hi = np.concatenate([hi.view(np.uint16), pad], axis=1).reshape(rows, kt, 32)
+    want_lo = np.concatenate([lo.view(np.uint16), pad], axis=1).reshape(rows, kt, 32)
     # signed zeros: RD(+0) = +0, RU(-0) = -0 and an exact value keeps its sign — numpy's nextafter path never runs there
     assert np.array_equal(got[:, :, 0, :], want_hi), np.argwhere(got[:, :, 0, :] != want_hi)[:5]
     assert np.array_equal(got[:, :, 1, :], want_lo), np.argwhere(got[:, :, 1, :] != want_lo)[:5]
