@@ -470,6 +470,23 @@ int skr_pearson_gemm_edges_needs_scratch(skr_ctx* ctx, const skr_operand* a, con
 int skr_topk_rows(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t col_begin, int64_t col_end,
                   int64_t row_global0, int64_t col_global0, int k, skr_mat* out_idx, skr_mat* out_val);
 
+/* Per-row top-k in one pass, with a running result: after the call io_idx[i, :] / io_val[i, :] hold the k best entries
+ * of the union of (a) the list they held on entry — ignored when first != 0; a slot with index 0xFFFFFFFF is no entry —
+ * and (b) the cells r[i, col_begin:col_end], minus the cell whose global column equals the global row when
+ * exclude_diag != 0.  Order: value descending, -0 == +0, NaN after every number, ties to the smaller GLOBAL column
+ * (col_global0 + c; skr_topk_rows breaks ties by the local column) — a total order, so a row merged panel by panel ends
+ * with the same list whatever the split.  Values keep the cells' own bits; unfilled slots are 0xFFFFFFFF / NaN
+ * (0x7FC00000).  *saw_nan (may be NULL; the call then does not wait for the device) = 1 when a cell that was read, the
+ * excluded diagonal cell aside, is NaN.  Every cell is read once, whatever k is.  1 <= k <= kmax of
+ * skr_topk_merge_limits and global columns below 0xFFFFFFFF, else SKR_ERR_INVALID.  io_idx: SKR_U32, io_val: SKR_F32,
+ * each at least nrows * k cells, row i at i * k.                                                                    */
+int skr_topk_merge_rows(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t col_begin, int64_t col_end,
+                        int64_t row_global0, int64_t col_global0, int exclude_diag, int k, int first,
+                        skr_mat* io_idx, skr_mat* io_val, int* saw_nan);
+/* The capacities of skr_topk_merge_rows' kernel: the largest k, and the number of candidates its buffer holds (the
+ * buffer and the list are sorted together before a sweep step of 1 024 cells that might not fit).  Either may be NULL. */
+int skr_topk_merge_limits(int* kmax, int* candidate_cap);
+
 /* ---------------------------------------------------------------- one-call host forms --- */
 /* The two reference calls of the hot path over caller-owned host buffers, for bindings that do
  * not want to manage device handles (both run the same kernels as the handle-based functions).

@@ -123,6 +123,8 @@ SIGNATURES = {
     "skr_pearson_gemm_edges": (_int, [_p, _p, _p, _p, _i64, _i64, C.c_float, _int, _p, _p, _p, C.POINTER(_i64)]),
     "skr_pearson_gemm_edges_needs_scratch": (_int, [_p, _p, _p, C.POINTER(_int)]),
     "skr_topk_rows": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _int, _p, _p]),
+    "skr_topk_merge_rows": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _p, _p, C.POINTER(_int)]),
+    "skr_topk_merge_limits": (_int, [C.POINTER(_int), C.POINTER(_int)]),
     "skr_mat_save_npy": (_int, [_p, _p, _int, C.c_char_p]),
     "skr_mat_save_csv": (_int, [_p, _p, _int, _int, C.c_char_p]),
     "skr_host_save_npy": (_int, [_p, _int, _i64, _i64, _int, C.c_char_p]),
@@ -1103,6 +1105,41 @@ def pearson(ctx, c1, c2, row_standardize=True, precision=PREC_FP32, r=None):
     r = ctx.empty(c1.rows, c2.rows, c1.dtype) if r is None else r
     check(lib().skr_pearson(ctx._h, c1._h, c2._h, 1 if row_standardize else 0, int(precision), r._h))
     return r
+
+
+# what skr_topk_merge_limits reports (csrc/topk.hip: kTopkKmax, kTopkCap, kTopkStep), mirrored here so that arguments
+# are refused before any device call and tests walk the kernel's real boundaries; tests compare the two
+TOPK_MERGE_KMAX = 256    # largest k of skr_topk_merge_rows
+TOPK_MERGE_CAP = 1792    # candidates its buffer holds
+TOPK_MERGE_STEP = 1024   # cells per sweep step: buffer and list are sorted when more than CAP - STEP candidates wait
+TOPK_PAD_IDX, TOPK_PAD_BITS = 0xFFFFFFFF, 0x7FC00000  # an unfilled slot
+
+
+def topk_merge_limits():
+    """(kmax, candidate_cap) as the library reports them."""
+    kmax, cap = _int(0), _int(0)
+    check(lib().skr_topk_merge_limits(C.byref(kmax), C.byref(cap)))
+    return kmax.value, cap.value
+
+
+def check_topk_k(k, what="k"):
+    """ValueError unless 1 <= k <= TOPK_MERGE_KMAX (no device call)."""
+    if int(k) != k or not 1 <= int(k) <= TOPK_MERGE_KMAX:
+        raise ValueError("{} must be an integer in 1..{} (got {!r})".format(what, TOPK_MERGE_KMAX, k))
+    return int(k)
+
+
+def topk_merge_rows(ctx, r, idx, val, k, first, nrows=None, col_begin=0, col_end=None, row_global0=0, col_global0=0,
+                    exclude_diag=True, want_nan=False):
+    """skr_topk_merge_rows: the k best of (the lists in idx / val, unless `first`) and the cells r[0:nrows,
+    col_begin:col_end] into idx / val (uint32 / float32 device matrices of at least nrows * k cells).  Returns saw_nan
+    (False without want_nan: the call then does not wait for the device)."""
+    nan = _int(0)
+    check(lib().skr_topk_merge_rows(ctx._h, r._h, int(r.rows if nrows is None else nrows), int(col_begin),
+                                    int(r.cols if col_end is None else col_end), int(row_global0), int(col_global0),
+                                    1 if exclude_diag else 0, int(k), 1 if first else 0, idx._h, val._h,
+                                    C.byref(nan) if want_nan else None))
+    return bool(nan.value)
 
 
 # ----------------------------------------------------------------------------- writers -----

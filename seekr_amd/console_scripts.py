@@ -1,6 +1,7 @@
 """`seekr_kmer_counts`, `seekr_pearson`, `seekr_norm_vectors` and `seekr_adj_pval` with the reference's flags
 (console_scripts.py:564-681, 887-918), and `seekr_domain_pearson` (sliding windows of a target against queries: no
-counterpart in the reference).  Only the commands on the hot path are provided."""
+counterpart in the reference) and `seekr_nearest` (the k most correlated rows of every row: likewise).  Only the commands
+on the hot path are provided."""
 import argparse
 import sys
 
@@ -75,6 +76,20 @@ Examples
 --------
     labelled CSV:   seekr_domain_pearson repeats.fa chrX_region.fa mean.npy std.npy -k 6 -w 1000 -s 100 -o r.csv
     .npy:           seekr_domain_pearson repeats.fa chrX_region.fa mean.npy std.npy -w 500 -s 50 -o r.npy -bo
+"""
+
+NEAREST_DOC = """
+Description
+-----------
+For every row of a k-mer count file, the rows of a second count file (or of the same one) it correlates with most,
+computed on an MI355X without the all-pairs matrix ever standing anywhere.  The output is a CSV with the columns
+row,rank,neighbor,r: rank 0 is the best neighbour; rows and neighbours are named by the labels of the count files, or
+by their indices for .npy input.  With one count file a row is not its own neighbour.
+
+Examples
+--------
+    ten neighbours within one file:    seekr_nearest counts.csv -o nearest.csv
+    three of b.npy for each of a.npy:  seekr_nearest a.npy b.npy -n 3 -o nearest.csv -bi
 """
 
 _LOG2 = ["Log2.post", "Log2.pre", "Log2.none"]
@@ -230,3 +245,38 @@ def console_domain_pearson():
     args = _parse_args_or_exit(parser)
     _run_domain_pearson(args.query, args.target, args.mean, args.std, int(args.kmer), int(args.window), int(args.slide),
                         args.log2, args.outfile, args.binary_output)
+
+
+def _run_nearest(counts1, counts2, neighbors, outfile, binary_input):
+    import csv
+    from seekr_amd import neighbors as neighbors_mod
+    names1 = names2 = None
+    same_file = counts2 is None or counts1 == counts2
+    if binary_input:  # read as _run_pearson reads them
+        counts1 = np.load(counts1)
+        counts2 = None if same_file else np.load(counts2)
+    else:
+        counts1, names1 = _read_labelled_csv(counts1)
+        counts2, names2 = (None, names1) if same_file else _read_labelled_csv(counts2)
+    idx, val = neighbors_mod.nearest(counts1, counts2, k=neighbors)
+    with open(outfile, "w", newline="") as f:
+        out = csv.writer(f, lineterminator="\n")
+        out.writerow(["row", "rank", "neighbor", "r"])
+        for i in range(idx.shape[0]):
+            for t in range(idx.shape[1]):
+                j = int(idx[i, t])
+                if j == _lib.TOPK_PAD_IDX:  # fewer candidates than neighbours asked for
+                    break
+                out.writerow([i if names1 is None else names1[i], t, j if names2 is None else names2[j], str(val[i, t])])
+
+
+def console_nearest():
+    parser = argparse.ArgumentParser(usage=NEAREST_DOC, formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    parser.add_argument("counts1", help="Count file whose rows are asked about.")
+    parser.add_argument("counts2", nargs="?", default=None,
+                        help="Count file the neighbours come from (default: counts1 itself, a row's own cell left out).")
+    parser.add_argument("-n", "--neighbors", default=10, help="Neighbours per row (at most %d)." % _lib.TOPK_MERGE_KMAX)
+    parser.add_argument("-o", "--outfile", default="nearest.csv", help="Where the list goes (CSV: row,rank,neighbor,r).")
+    parser.add_argument("-bi", "--binary_input", action="store_true", help="The count files are .npy, not labelled CSV.")
+    args = _parse_args_or_exit(parser)
+    _run_nearest(args.counts1, args.counts2, int(args.neighbors), args.outfile, args.binary_input)

@@ -7,6 +7,8 @@ it: keeping these reductions on the GPU avoids shipping an N x N m
     empirical_pvalues     find_pval.py:158-164   p[i,j] = np.sum(fitres > sim[i,j]) / len(fitres)
     edges / pearson_edges kmer_leiden.py:91-96   the thresholded matrix as an edge list, r produced and consumed
                                                  one row stripe at a time (N x N never exists)
+    topk_rows / pearson_topk  —                  the k most correlated rows of every row; pearson_topk merges r block by
+                                                 block into running lists (N x N never exists)
     adjust_pvalues        adj_pval.py:53-138     multipletests on the p-value matrix (symmetric: upper triangle)
 
 Every function takes and returns device matrices (`seekr_amd._lib.Matrix`); `*_host` helpers
@@ -199,6 +201,47 @@ def topk_rows(r, k, nrows=None, col_begin=0, col_end=None, row_global0=0, col_gl
     idx.free()
     val.free()
     return out
+
+
+def pearson_topk(a, b=None, k=10, stripe_rows=8192, panel_rows=None):
+    """(idx uint32 [a.rows, k], val float32 [a.rows, k]): for every row of the prepared operand `a` (seekr_amd._lib.Operand)
+    the k rows of `b` it correlates with most, best first — np.argsort(-r[i], kind="stable")[:k] of r = a b^T / K with
+    NaN last and ties to the smaller row of b; rows with fewer than k candidates are padded with 0xFFFFFFFF / NaN.
+    b=None: `a` against itself, a row's own cell excluded.
+
+    r never stands whole: per stripe of `stripe_rows` rows of a, each panel of `panel_rows` rows of b (None: all of b) is
+    contracted into one reusable [stripe_rows, panel_rows] buffer and merged into the stripe's running lists
+    (skr_topk_merge_rows: one read of the buffer, whatever k is); only the finished [stripe, k] lists cross PCIe.
+    Device memory is stripe_rows x panel_rows floats plus the lists.  The order is total, so the result does not depend
+    on either split.  Operands of either kind (split halves or float32 layout) run the same two steps, as pearson_edges'
+    two-step path does.  Not done here: the self-comparison contracts every block, not half of them (r's symmetry is
+    not used), and the selection is a pass of its own over the buffer, not part of the contraction's epilogue."""
+    k = _lib.check_topk_k(k)
+    ctx = a.ctx
+    self_cmp = b is None
+    b = a if self_cmp else b
+    n, m = a.rows, b.rows
+    out_idx = np.full((n, k), _lib.TOPK_PAD_IDX, dtype=np.uint32)
+    out_val = np.full((n, k), np.uint32(_lib.TOPK_PAD_BITS), dtype=np.uint32).view(np.float32)
+    if n == 0 or m == 0:
+        return out_idx, out_val
+    stripe_rows = max(1, min(int(stripe_rows), n))
+    panel_rows = m if panel_rows is None else max(1, min(int(panel_rows), m))
+    buf = ctx.empty(stripe_rows, panel_rows)
+    idx, val = ctx.empty(stripe_rows, k, np.uint32), ctx.empty(stripe_rows, k, np.float32)
+    for s0 in range(0, n, stripe_rows):
+        rows = min(stripe_rows, n - s0)
+        a_s = a if rows == n else a.view(s0, rows)
+        for p0 in range(0, m, panel_rows):
+            cols = min(panel_rows, m - p0)
+            _lib.pearson_gemm_op(ctx, a_s, b if cols == m else b.view(p0, cols), buf)
+            _lib.topk_merge_rows(ctx, buf, idx, val, k, first=p0 == 0, nrows=rows, col_begin=0, col_end=cols,
+                                 row_global0=s0, col_global0=p0, exclude_diag=self_cmp)
+        idx.to_numpy(0, rows, out=out_idx[s0:s0 + rows])
+        val.to_numpy(0, rows, out=out_val[s0:s0 + rows])
+    for mat in (buf, idx, val):
+        mat.free()
+    return out_idx, out_val
 
 
 FUSE_MAX_DENSITY = 1e-3  # edges per cell above which the fused epilogue costs more than writing the stripe (measured: 100 000 rows, k = 6)

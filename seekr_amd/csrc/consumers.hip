@@ -9,6 +9,7 @@
 
 #include "common.hpp"
 #include "radix.hpp"
+#include "topk_key.hpp"
 
 namespace {
 
@@ -152,15 +153,6 @@ __global__ __launch_bounds__(256) void edges_fill_kernel(EdgeArgs a, const unsig
 // smaller column — np.argsort(-row, kind="stable")[:k] with NaN last and the row's own (global)
 // diagonal cell excluded.  One workgroup per row; k selection passes over the row (it stays in the
 // L2): pass t finds the largest key below the t-1-th winner.  Keys order (value desc, column asc).
-__device__ __forceinline__ unsigned long long topk_key(float v, uint32_t col) {
-    // monotone map of the float to uint32 (larger float -> larger key), NaN to the smallest key;
-    // the low word prefers the smaller column on equal values
-    uint32_t b = __float_as_uint(v == 0.f ? 0.f : v);  // -0 and +0 compare equal
-    b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    if (v != v) b = 0u;
-    return ((unsigned long long)b << 32) | (0xFFFFFFFFu - col);
-}
-
 __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict__ r, int64_t ld, int64_t rows,
                                                         int64_t col_begin, int64_t col_end, int64_t row_global0,
                                                         int64_t col_global0, int k, uint32_t* __restrict__ out_idx,

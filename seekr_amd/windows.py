@@ -157,6 +157,75 @@ class _Side:
         return view, has_nan
 
 
+class _DomainRun:
+    """The loop domain_pearson and domain_topk share: the target packed and its window table, the query operand filled
+    once, and per chunk of window rows count -> normalise -> operand fill -> contraction into one reusable block."""
+
+    def __init__(self, query, target, k, window, slide, mean, std, log2, chunk_rows, what):
+        mean, std = _fixed_vector(mean, "mean"), _fixed_vector(std, "std")
+        cols = 4 ** k
+        qmat = None
+        if not isinstance(query, (str, bytes, os.PathLike)):  # (checked first: reading the target already packs it on the device)
+            qmat = np.asarray(query)
+            if qmat.ndim != 2 or qmat.shape[1] != cols or qmat.dtype != np.float32:
+                raise ValueError("a query given as counts must be a float32 matrix of {} columns".format(cols))
+        holder = _holder(target, k, log2, "AGTC")
+        if holder.infasta is None:
+            raise TypeError("{} takes the target as a FASTA path".format(what))
+        ctx = holder._ctx()
+        if qmat is None:
+            qc = BasicCounter(os.fspath(query), k=k, mean=mean, std=std, log2=log2, silent=True)
+            qc.get_counts()
+            qmat = qc.counts
+        packed = holder._packed_seqs()
+        self.seq_index, self.start, self.length = window_table(packed.lengths(), window, slide)
+        self.n_rows, self.n_query = len(self.seq_index), qmat.shape[0]
+        self.chunk_rows = max(1, min(int(chunk_rows), max(self.n_rows, 1)))
+        self.holder, self.ctx, self.cols, self.qmat, self.packed = holder, ctx, cols, qmat, packed
+        self.k, self.window, self.slide, self.log2 = k, window, slide, log2
+        self.center, self.scale = _as_device_vector(ctx, mean, cols, None), _as_device_vector(ctx, std, cols, None)
+
+    def blocks(self):
+        """(r0, n, r_dev, has_nan) per chunk: r_dev[:, :n] holds r of every query against window rows r0 .. r0 + n - 1
+        (a [n_query, chunk_rows] block, overwritten by the next chunk); has_nan: the chunk's fill reported NaN."""
+        ctx, cols, k, log2, chunk_rows = self.ctx, self.cols, self.k, self.log2, self.chunk_rows
+        chunks = _chunks(self.n_rows, chunk_rows)
+        center, scale = self.center, self.scale
+        cnt = ctx.empty(chunk_rows, cols)
+
+        def counted(r0, n):
+            out = cnt if n == chunk_rows else cnt.view(0, n)
+            return _lib.count_windows(ctx, self.packed, k, self.window, self.slide, r0, n, log2_pre=(log2 == "Log2.pre"), out=out)
+
+        post, shift = log2 == "Log2.post", np.float32(0.0)
+        if post:  # np.min over the whole normalised matrix (NaN-propagating), chunk by chunk
+            lowest = np.float32(np.inf)
+            for r0, n in chunks:
+                mn, _ = _lib.min_nan(ctx, counted(r0, n), center, scale)
+                lowest = np.minimum(lowest, mn)
+            shift = np.abs(lowest)
+        precision = pearson_mod._precision_for(np.dtype(np.float32), True)
+        qdev = ctx.from_numpy(self.qmat)
+        qside, tside = _Side(ctx, self.n_query, cols, precision), _Side(ctx, chunk_rows, cols, precision)
+        q_op, _ = qside.fill(qdev, precision)
+        if q_op.kind == 0:
+            precision = _lib.PREC_FP32
+        r_dev = ctx.empty(self.n_query, chunk_rows)
+        for r0, n in chunks:
+            x = counted(r0, n)
+            tail = dict(center=center, scale=scale, post=post, shift=float(shift))
+            t_op, has_nan = tside.fill(x, precision, **tail)
+            a_op = q_op
+            if t_op.kind != q_op.kind:  # rows the split layouts do not carry: this chunk in float32 layout on both sides
+                t_op, has_nan = tside.fill(x, _lib.PREC_FP32, **tail)
+                a_op, _ = qside.fill(qdev, _lib.PREC_FP32)
+            _lib.pearson_gemm_op(ctx, a_op, t_op, r_dev)
+            yield r0, n, r_dev, has_nan
+
+    def headers(self):
+        return np.asarray(_headers(self.holder), dtype=object)
+
+
 @_lib.api_call
 def domain_pearson(query, target, k, window, slide, mean, std, log2="Log2.post", chunk_rows=65536, outfile=None):
     """Pearson r between every query and every sliding window of the target: (r float32 [n_query, n_windows], table).
@@ -169,67 +238,53 @@ def domain_pearson(query, target, k, window, slide, mean, std, log2="Log2.post",
     for that minimum, once for r.  table: DataFrame with `header`, `start`, `end` of every window (the columns of r).
     NAN_WARNING is printed once when a chunk's normalised counts or its block of r hold NaN.  outfile: r is also saved there
     as .npy."""
-    mean, std = _fixed_vector(mean, "mean"), _fixed_vector(std, "std")
-    holder = _holder(target, k, log2, "AGTC")
-    if holder.infasta is None:
-        raise TypeError("domain_pearson takes the target as a FASTA path")
-    ctx = holder._ctx()
-    cols = 4 ** k
-    if isinstance(query, (str, bytes, os.PathLike)):
-        qc = BasicCounter(os.fspath(query), k=k, mean=mean, std=std, log2=log2, silent=True)
-        qc.get_counts()
-        qmat = qc.counts
-    else:
-        qmat = np.asarray(query)
-        if qmat.ndim != 2 or qmat.shape[1] != cols or qmat.dtype != np.float32:
-            raise ValueError("a query given as counts must be a float32 matrix of {} columns".format(cols))
-    packed = holder._packed_seqs()
-    seq_index, start, length = window_table(packed.lengths(), window, slide)
-    n_rows, n_query = len(seq_index), qmat.shape[0]
-    chunk_rows = max(1, min(int(chunk_rows), max(n_rows, 1)))
-    chunks = _chunks(n_rows, chunk_rows)
-    center, scale = _as_device_vector(ctx, mean, cols, None), _as_device_vector(ctx, std, cols, None)
-    cnt = ctx.empty(chunk_rows, cols)
-
-    def counted(r0, n):
-        out = cnt if n == chunk_rows else cnt.view(0, n)
-        return _lib.count_windows(ctx, packed, k, window, slide, r0, n, log2_pre=(log2 == "Log2.pre"), out=out)
-
-    post, shift, nan_seen = log2 == "Log2.post", np.float32(0.0), False
-    if post:  # np.min over the whole normalised matrix (NaN-propagating), chunk by chunk
-        lowest = np.float32(np.inf)
-        for r0, n in chunks:
-            mn, _ = _lib.min_nan(ctx, counted(r0, n), center, scale)
-            lowest = np.minimum(lowest, mn)
-        shift = np.abs(lowest)
-    precision = pearson_mod._precision_for(np.dtype(np.float32), True)
-    qdev = ctx.from_numpy(qmat)
-    qside, tside = _Side(ctx, n_query, cols, precision), _Side(ctx, chunk_rows, cols, precision)
-    q_op, _ = qside.fill(qdev, precision)
-    if q_op.kind == 0:
-        precision = _lib.PREC_FP32
-    r = np.empty((n_query, n_rows), dtype=np.float32)
-    r_dev = ctx.empty(n_query, chunk_rows)
-    for r0, n in chunks:
-        x = counted(r0, n)
-        tail = dict(center=center, scale=scale, post=post, shift=float(shift))
-        t_op, has_nan = tside.fill(x, precision, **tail)
-        a_op = q_op
-        if t_op.kind != q_op.kind:  # rows the split layouts do not carry: this chunk in float32 layout on both sides
-            t_op, has_nan = tside.fill(x, _lib.PREC_FP32, **tail)
-            a_op, _ = qside.fill(qdev, _lib.PREC_FP32)
-        nan_seen = nan_seen or has_nan
-        _lib.pearson_gemm_op(ctx, a_op, t_op, r_dev)
+    run = _DomainRun(query, target, k, window, slide, mean, std, log2, chunk_rows, "domain_pearson")
+    n_rows, nan_seen = run.n_rows, False
+    r = np.empty((run.n_query, n_rows), dtype=np.float32)
+    for r0, n, r_dev, has_nan in run.blocks():
         r[:, r0:r0 + n] = r_dev.to_numpy()[:, :n]
         # a constant row (a window of fewer than k letters under mean 0 / std 1) has finite counts and no r
-        nan_seen = nan_seen or bool(np.isnan(r[:, r0:r0 + n]).any())
+        nan_seen = nan_seen or has_nan or bool(np.isnan(r[:, r0:r0 + n]).any())
     if nan_seen:
         print(NAN_WARNING)
-    headers = np.asarray(_headers(holder), dtype=object)
-    table = _frame({"header": headers[seq_index] if n_rows else headers[:0], "start": start, "end": start + length})
+    headers = run.headers()
+    table = _frame({"header": headers[run.seq_index] if n_rows else headers[:0], "start": run.start,
+                    "end": run.start + run.length})
     if outfile:
         _lib.save_npy(outfile, r)
     return r, table
+
+
+@_lib.api_call
+def domain_topk(query, target, k, window, slide, mean, std, top=10, log2="Log2.post", chunk_rows=65536):
+    """The `top` windows of the target each query correlates with most: a DataFrame with one row per (query, rank) and the
+    columns `query` (its index), `rank` (0 = best), `header`, `start`, `end` (the window) and `r` — the first `top`
+    entries of np.argsort(-r[q], kind="stable") of domain_pearson's r for the same arguments, NaN last, ties to the
+    earlier window.  domain_pearson's loop with one change: each chunk's block of r is merged into the queries' running
+    lists on the device (skr_topk_merge_rows) and r is never downloaded — top x n_query entries cross PCIe instead of
+    n_query x n_windows floats.  Fewer than `top` windows: fewer rows.  NAN_WARNING as in domain_pearson."""
+    top = _lib.check_topk_k(top, "top")
+    run = _DomainRun(query, target, k, window, slide, mean, std, log2, chunk_rows, "domain_topk")
+    ctx, nan_seen = run.ctx, False
+    idx, val = ctx.empty(run.n_query, top, np.uint32), ctx.empty(run.n_query, top, np.float32)
+    first = True
+    for r0, n, r_dev, has_nan in run.blocks():
+        saw = _lib.topk_merge_rows(ctx, r_dev, idx, val, top, first=first, col_begin=0, col_end=n, col_global0=r0,
+                                   exclude_diag=False, want_nan=True)
+        nan_seen, first = nan_seen or has_nan or saw, False
+    if nan_seen:
+        print(NAN_WARNING)
+    if first or run.n_query == 0:  # no window or no query
+        win, rv = np.empty(0, np.int64), np.empty(0, np.float32)
+        qi = rank = win
+    else:
+        hi, hv = idx.to_numpy(), val.to_numpy()
+        keep = hi != _lib.TOPK_PAD_IDX  # padded slots are dropped
+        qi, rank = np.nonzero(keep)
+        win, rv = hi[keep].astype(np.int64), hv[keep]
+    headers = run.headers()
+    return _frame({"query": qi, "rank": rank, "header": headers[run.seq_index[win]] if len(win) else headers[:0],
+                   "start": run.start[win], "end": run.start[win] + run.length[win], "r": rv})
 
 
 def window_labels(table):

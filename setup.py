@@ -18,6 +18,8 @@ setup(
             "seekr_adj_pval = seekr_amd.console_scripts:console_adj_pval",
             # sliding windows of a target against queries (no counterpart in the reference)
             "seekr_domain_pearson = seekr_amd.console_scripts:console_domain_pearson",
+            # the k most correlated rows of every row, without the all-pairs matrix (no counterpart either)
+            "seekr_nearest = seekr_amd.console_scripts:console_nearest",
         ]
     },
 )
