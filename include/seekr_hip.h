@@ -487,6 +487,32 @@ int skr_topk_merge_rows(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t c
  * buffer and the list are sorted together before a sweep step of 1 024 cells that might not fit).  Either may be NULL. */
 int skr_topk_merge_limits(int* kmax, int* candidate_cap);
 
+/* ---------------------------------------------------------------- communities (Leiden) -- */
+/* Communities of an undirected weighted graph (the step kmer_leiden.py:131-146 hands to leidenalg.find_partition), on the
+ * device: local moving, refinement and aggregation, level after level (seekr_amd/csrc/leiden.hip, DESIGN_KERNELS.md).
+ * The graph is the upper-triangle list skr_pearson_gemm_edges / skr_edges give with upper_only: rows / cols SKR_U32 with
+ * row < col < n_nodes, vals SKR_F32 > 0, any order, no duplicates, n_edges entries each.  row >= col, a weight that is
+ * zero, negative, NaN or infinite, and an index >= n_nodes are refused with SKR_ERR_INVALID (checked on the device).
+ * quality: what is maximised, with w_c the weight inside community c, K_c the sum of weighted degrees in c, n_c the
+ * number of nodes in c, m the total edge weight and g = resolution:
+ *   0 RBConfigurationVertexPartition   sum_c (w_c - g K_c^2 / (4 m))
+ *   1 ModularityVertexPartition        the same with g = 1, reported divided by m
+ *   2 RBERVertexPartition              sum_c (w_c - g p n_c (n_c - 1) / 2),  p = m / (n (n - 1) / 2)
+ *   3 CPMVertexPartition               sum_c (w_c - g n_c (n_c - 1) / 2)
+ * membership: SKR_U32, at least n_nodes cells; communities are numbered by size, largest first, ties to the community
+ * holding the smallest node.  *quality_out: the function above for the returned membership, a float64 sum in a fixed
+ * order.  The same input gives the same bits on every run.  Every returned community is connected in the graph.
+ * max_levels bounds the levels, max_sweeps the sweeps of one level's local moving and the rounds of its refinement;
+ * skr_leiden_last tells whether the calling thread's last run ended by itself (*converged = 1) or at a bound, and how
+ * many sweeps it applied.  skr_leiden_limits: the largest degree the one-wave-per-node and the LDS-table work units
+ * take (larger degrees use a table in the ctx workspace).  Either pointer of the last two functions may be NULL.     */
+int skr_leiden(skr_ctx* ctx, const skr_mat* rows, const skr_mat* cols, const skr_mat* vals, int64_t n_edges,
+               int64_t n_nodes, int quality, double resolution, int max_levels, int max_sweeps,
+               skr_mat* membership /* int32 [n_nodes,1] */, double* quality_out, int64_t* n_communities,
+               int64_t* levels_run);
+int skr_leiden_last(int* converged, int64_t* sweeps);
+int skr_leiden_limits(int* wave_degree, int* lds_degree);
+
 /* ---------------------------------------------------------------- one-call host forms --- */
 /* The two reference calls of the hot path over caller-owned host buffers, for bindings that do
  * not want to manage device handles (both run the same kernels as the handle-based functions).

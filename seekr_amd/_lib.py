@@ -125,6 +125,10 @@ SIGNATURES = {
     "skr_topk_rows": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _int, _p, _p]),
     "skr_topk_merge_rows": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _p, _p, C.POINTER(_int)]),
     "skr_topk_merge_limits": (_int, [C.POINTER(_int), C.POINTER(_int)]),
+    "skr_leiden": (_int, [_p, _p, _p, _p, _i64, _i64, _int, C.c_double, _int, _int, _p, C.POINTER(C.c_double), C.POINTER(_i64),
+                          C.POINTER(_i64)]),
+    "skr_leiden_last": (_int, [C.POINTER(_int), C.POINTER(_i64)]),
+    "skr_leiden_limits": (_int, [C.POINTER(_int), C.POINTER(_int)]),
     "skr_mat_save_npy": (_int, [_p, _p, _int, C.c_char_p]),
     "skr_mat_save_csv": (_int, [_p, _p, _int, _int, C.c_char_p]),
     "skr_host_save_npy": (_int, [_p, _int, _i64, _i64, _int, C.c_char_p]),

@@ -1,7 +1,8 @@
 """`seekr_kmer_counts`, `seekr_pearson`, `seekr_norm_vectors` and `seekr_adj_pval` with the reference's flags
 (console_scripts.py:564-681, 887-918), and `seekr_domain_pearson` (sliding windows of a target against queries: no
-counterpart in the reference) and `seekr_nearest` (the k most correlated rows of every row: likewise).  Only the commands
-on the hot path are provided."""
+counterpart in the reference) and `seekr_nearest` (the k most correlated rows of every row: likewise), and
+`seekr_kmer_leiden` with the reference's flags (console_scripts.py:1033-1101) plus --edges.  Only the commands on the hot
+path are provided."""
 import argparse
 import sys
 
@@ -280,3 +281,46 @@ def console_nearest():
     parser.add_argument("-bi", "--binary_input", action="store_true", help="The count files are .npy, not labelled CSV.")
     args = _parse_args_or_exit(parser)
     _run_nearest(args.counts1, args.counts2, int(args.neighbors), args.outfile, args.binary_input)
+
+
+KMER_LEIDEN_DOC = """
+Description
+-----------
+Leiden communities of the sequences of a FASTA file on an MI355X: k-mer counts, Pearson correlation, threshold and
+partition all run on the device.  Flags are those of the reference command of the same name; the network plot is not
+built (-pn is refused: write the CSV files with -cf and plot from them), the result is the same on every run (-sd is
+accepted and changes nothing), and --edges nonzero writes only the kept edges.
+
+Examples
+--------
+    communities at r >= 0.05, CSV files:   seekr_kmer_leiden seqs.fa mean.npy std.npy 4 -pco 0.05 -cf out
+    modularity, kept edges only:           seekr_kmer_leiden seqs.fa mean.npy std.npy 6 -a ModularityVertexPartition -cf out --edges nonzero
+"""
+
+
+def console_kmer_leiden():
+    from seekr_amd import kmer_leiden
+    parser = argparse.ArgumentParser(usage=KMER_LEIDEN_DOC, formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    parser.add_argument("fasta", help="full path of the input fasta sequence file; the headers label the nodes.")
+    parser.add_argument("mean_path", help="full path to the normalization mean vector numpy file.")
+    parser.add_argument("std_path", help="full path to the normalization std vector numpy file.")
+    parser.add_argument("kmer", help="length of kmers, consistent with the mean and std vector files.")
+    parser.add_argument("-a", "--algo", default="RBERVertexPartition",
+                        choices=["ModularityVertexPartition", "RBConfigurationVertexPartition", "RBERVertexPartition", "CPMVertexPartition",
+                                 "SurpriseVertexPartition", "SignificanceVertexPartition"],
+                        help="the quality function the communities maximise (Surprise and Significance are not built).")
+    parser.add_argument("-r", "--rs", default=1.0, help="the resolution parameter, larger value leads to more clusters.")
+    parser.add_argument("-pco", "--pearsoncutoff", default=0.0, help="set to 0 pearson correlation r values that are less than the pearsoncutoff.")
+    parser.add_argument("-sd", "--setseed", action="store_true", help="accepted for compatibility: the result is always reproducible.")
+    parser.add_argument("-ec", "--edgecolormethod", default="gradient", choices=["gradient", "threshold"], help="plot option (the plot is not built).")
+    parser.add_argument("-et", "--edgethreshold", default=0.1, help="plot option (the plot is not built).")
+    parser.add_argument("-lfs", "--labelfontsize", default=12, help="plot option (the plot is not built).")
+    parser.add_argument("-pn", "--plotname", default=None, help="not built: any value is refused; use --csvfile.")
+    parser.add_argument("-cf", "--csvfile", default=None,
+                        help="name and path of the nodes and edges csv files; _nodes_leiden.csv and _edges_leiden.csv are appended.")
+    parser.add_argument("--edges", default="all", choices=["all", "nonzero"],
+                        help="edges file: every upper-triangle cell, zeros included (the reference), or the kept edges only.")
+    args = _parse_args_or_exit(parser)
+    kmer_leiden.kmer_leiden(args.fasta, args.mean_path, args.std_path, int(args.kmer), args.algo, float(args.rs), float(args.pearsoncutoff),
+                            args.setseed, args.edgecolormethod, float(args.edgethreshold), int(args.labelfontsize), args.plotname,
+                            args.csvfile, edges=args.edges)

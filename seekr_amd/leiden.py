@@ -1,0 +1,106 @@
+"""Leiden communities of an edge list on MI355X (skr_leiden): the step kmer_leiden.py:131-146 of the reference hands to
+leidenalg.find_partition.  The reference draws a random visiting order (setseed=False is its default), so there are no
+bits to match: the result here is the same on every run, every community is connected, and its quality is measured
+against a sequential Louvain (tests/leiden_cases.py).  DESIGN_PARITY.md lists the quality functions.
+"""
+import ctypes as C
+
+import numpy as np
+
+from seekr_amd import _lib
+
+ALGOS = {"RBConfigurationVertexPartition": 0, "ModularityVertexPartition": 1, "RBERVertexPartition": 2, "CPMVertexPartition": 3}
+NOT_BUILT = ("SurpriseVertexPartition", "SignificanceVertexPartition")
+
+
+def algo_code(algo):
+    """The `quality` id of skr_leiden; NotImplementedError for the two functions that are not built."""
+    if algo in NOT_BUILT:
+        raise NotImplementedError("{} is not built on the device (nor is {}); use one of {}".format(
+            algo, [a for a in NOT_BUILT if a != algo][0], ", ".join(sorted(ALGOS))))
+    if algo not in ALGOS:
+        raise ValueError("unknown algo {!r}; one of {}".format(algo, ", ".join(sorted(ALGOS))))
+    return ALGOS[algo]
+
+
+def limits():
+    """(wave_degree, lds_degree): the largest degree the one-wave-per-node and the LDS-table work units take, as the
+    library reports them (skr_leiden_limits)."""
+    a, b = C.c_int(0), C.c_int(0)
+    _lib.check(_lib.lib().skr_leiden_limits(C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def _column(ctx, x, dtype):
+    """A device column of `dtype`: device matrices pass through, anything else is uploaded.  Returns (matrix, owned)."""
+    if isinstance(x, _lib.Matrix):
+        if x.dtype != np.dtype(dtype):
+            raise TypeError("device edge lists are uint32, uint32, float32 (got {})".format(x.dtype))
+        return x, False
+    a = np.ascontiguousarray(x).reshape(-1)
+    if np.dtype(dtype) == np.uint32 and len(a) and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+        raise ValueError("node indices must fit 32 bits and be >= 0")
+    a = a.astype(dtype, copy=False)
+    m = ctx.empty(max(len(a), 1), 1, dtype)
+    if len(a):
+        m.upload(a.reshape(-1, 1))
+    return m, True
+
+
+@_lib.api_call
+def communities(rows, cols, vals, n_nodes, algo="RBERVertexPartition", rs=1.0, max_levels=32, max_sweeps=64, n_edges=None):
+    """(membership int32 [n_nodes], quality float, info dict) of the undirected weighted graph given as the
+    upper-triangle list pearson_edges(..., upper_only=True) returns: row < col, weight > 0, any order, no duplicates;
+    numpy arrays (uploaded) or device matrices (`n_edges`: how many of their cells are the list; default all).
+    Communities are numbered by size, largest first, ties to the community holding the smallest node.  `quality` is the
+    function `algo` names (RBConfigurationVertexPartition, ModularityVertexPartition, RBERVertexPartition,
+    CPMVertexPartition) for the returned membership; `rs` is its resolution (ignored by ModularityVertexPartition).
+    info: n_communities, levels, sweeps, converged (False when max_levels or max_sweeps ended the run)."""
+    code = algo_code(algo)
+    ctx = _lib.default_context()
+    for x in (rows, cols, vals):
+        if isinstance(x, _lib.Matrix):
+            ctx = x.ctx
+    owned = []
+    try:
+        mats = []
+        for x, dt in ((rows, np.uint32), (cols, np.uint32), (vals, np.float32)):
+            m, own = _column(ctx, x, dt)
+            mats.append(m)
+            if own:
+                owned.append(m)
+        if n_edges is None:
+            n_edges = 0 if not isinstance(rows, _lib.Matrix) and np.size(rows) == 0 else mats[0].rows * mats[0].cols
+        n_nodes = int(n_nodes)
+        mem = ctx.empty(max(n_nodes, 1), 1, np.uint32)
+        owned.append(mem)
+        q, nc, lv = C.c_double(0), C.c_int64(0), C.c_int64(0)
+        _lib.check(_lib.lib().skr_leiden(ctx._h, mats[0]._h, mats[1]._h, mats[2]._h, int(n_edges), n_nodes, code, C.c_double(float(rs)),
+                                         int(max_levels), int(max_sweeps), mem._h, C.byref(q), C.byref(nc), C.byref(lv)))
+        conv, sweeps = C.c_int(1), C.c_int64(0)
+        _lib.check(_lib.lib().skr_leiden_last(C.byref(conv), C.byref(sweeps)))
+        membership = mem.to_numpy(0, n_nodes).reshape(-1).view(np.int32).copy() if n_nodes else np.empty(0, np.int32)
+    finally:
+        for m in owned:
+            m.free()
+    return membership, q.value, {"n_communities": nc.value, "levels": lv.value, "sweeps": sweeps.value, "converged": bool(conv.value)}
+
+
+def pearson_communities(z, cutoff=0.0, algo="RBERVertexPartition", rs=1.0, max_levels=32, max_sweeps=64, **kw):
+    """communities() of the thresholded self-comparison of the prepared operand `z` (seekr_amd._lib.Operand): edge
+    {i, j} weighs r[i, j] where !(r < cutoff), r > 0 and i != j (kmer_leiden.py:94-96, 106-107).  r never stands whole:
+    consumers.pearson_edges reduces it to the edge list stripe by stripe.  That function hands the list back in host
+    memory (each stripe's edges are downloaded as they are found), so here the finished list is UPLOADED once for
+    skr_leiden — it does not stay on the device between the two steps.  `kw`: stripe_rows, fuse of pearson_edges.
+    Returns (membership, quality, info) with info["n_edges"] added."""
+    from seekr_amd import consumers
+    algo_code(algo)
+    rows, cols, vals = consumers.pearson_edges(z, cutoff, upper_only=True, **kw)
+    keep = vals > 0  # a negative cutoff keeps negative cells and NaN passes the mask: neither is an edge weight
+    if not keep.all():
+        rows, cols, vals = rows[keep], cols[keep], vals[keep]
+    membership, quality, info = communities(rows.astype(np.uint32), cols.astype(np.uint32), vals.astype(np.float32), z.rows, algo=algo,
+                                            rs=rs, max_levels=max_levels, max_sweeps=max_sweeps)
+    info["n_edges"] = int(len(vals))
+    info["edges"] = (rows, cols, vals)
+    return membership, quality, info

@@ -20,6 +20,7 @@ setup(
             "seekr_domain_pearson = seekr_amd.console_scripts:console_domain_pearson",
             # the k most correlated rows of every row, without the all-pairs matrix (no counterpart either)
             "seekr_nearest = seekr_amd.console_scripts:console_nearest",
+            "seekr_kmer_leiden = seekr_amd.console_scripts:console_kmer_leiden",
         ]
     },
 )
