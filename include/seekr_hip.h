@@ -432,6 +432,25 @@ int skr_pvals_symmetric(skr_ctx* ctx, const skr_mat* p, int* symmetric);
  * p-values are outside the contract.  No tests: SKR_ERR_ZERODIV; hommel above 2^22 tests: SKR_ERR_UNSUPPORTED;
  * a workspace larger than the free device memory: SKR_ERR_NOMEM with the bytes needed.                       */
 int skr_adjust_pvalues(skr_ctx* ctx, const skr_mat* p, int method, double alpha, int upper_only, skr_mat* out);
+/* The correction of the smallest p-values of a longer list.  p (a vector of E float32 or float64 cells, any order)
+ * holds the E smallest of ntests >= E tests; the ntests - E missing ones count as larger than every given one.
+ * out[i] (float64, E cells) = what skr_adjust_pvalues(upper_only = 1) computes for that test among all ntests: the
+ * formulas take ntests as the number of tests, the sort, the scans and the write-back run over the E given ones, and the
+ * running minimum from the end (simes-hochberg, fdr_bh, fdr_by) starts at the last given test.  For bonferroni, sidak,
+ * holm-sidak, holm, simes-hochberg, fdr_bh and fdr_by every corrected value <= alpha of the full list depends on tests
+ * with p <= alpha and on ntests only, so a head that holds every p <= alpha gives those values bit for bit
+ * (DESIGN_PARITY.md).  hommel, fdr_tsbh, fdr_tsbky, fdr_gbs: SKR_ERR_UNSUPPORTED (their values depend on the tests left
+ * out).  ntests < E: SKR_ERR_INVALID; ntests = 0: SKR_ERR_ZERODIV; E = 0 < ntests: nothing is written.  Workspace as
+ * skr_adjust_pvalues (SKR_ERR_NOMEM with the bytes needed).                                                        */
+int skr_adjust_pvalues_head(skr_ctx* ctx, const skr_mat* p, int64_t ntests, int method, double alpha, skr_mat* out);
+
+/* Stable selection: the positions i (ascending) of the float32 / float64 vector `values` with (double)values[i] <=
+ * bound; NaN never passes.  *count receives their number; with out_index (SKR_U32, at least *count cells) non-NULL
+ * they are written, with NULL only the count is made (the count-then-write pair of skr_edges).  At most 2^32 cells. */
+int skr_select_le(skr_ctx* ctx, const skr_mat* values, double bound, skr_mat* out_index, int64_t* count);
+/* out[i] = src[index[i]] for i < count: src a vector of SKR_U32, SKR_F32 or SKR_F64 cells, index SKR_U32 (as
+ * skr_select_le writes it), out of src's dtype; an index outside src: SKR_ERR_INVALID.                              */
+int skr_gather_index(skr_ctx* ctx, const skr_mat* src, const skr_mat* index, int64_t count, skr_mat* out);
 
 /* The non-zero cells that kmer_leiden.py:94-96 leaves in a block of r, as an edge list and
  * without writing the zeros: cells of r[0:nrows, col_begin:col_end] with !(v < cutoff) (NaN

@@ -119,6 +119,9 @@ SIGNATURES = {
     "skr_parametric_pvalues": (_int, [_p, _p, C.c_char_p, C.POINTER(C.c_double), _int, _p]),
     "skr_pvals_symmetric": (_int, [_p, _p, C.POINTER(_int)]),
     "skr_adjust_pvalues": (_int, [_p, _p, _int, C.c_double, _int, _p]),
+    "skr_adjust_pvalues_head": (_int, [_p, _p, _i64, _int, C.c_double, _p]),
+    "skr_select_le": (_int, [_p, _p, C.c_double, _p, C.POINTER(_i64)]),
+    "skr_gather_index": (_int, [_p, _p, _p, _i64, _p]),
     "skr_edges": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, C.c_float, _int, _p, _p, _p, C.POINTER(_i64)]),
     "skr_pearson_gemm_edges": (_int, [_p, _p, _p, _p, _i64, _i64, C.c_float, _int, _p, _p, _p, C.POINTER(_i64)]),
     "skr_pearson_gemm_edges_needs_scratch": (_int, [_p, _p, _p, C.POINTER(_int)]),

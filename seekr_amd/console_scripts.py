@@ -1,6 +1,7 @@
 """`seekr_kmer_counts`, `seekr_pearson`, `seekr_norm_vectors` and `seekr_adj_pval` with the reference's flags
 (console_scripts.py:564-681, 887-918), and `seekr_domain_pearson` (sliding windows of a target against queries: no
-counterpart in the reference) and `seekr_nearest` (the k most correlated rows of every row: likewise), and
+counterpart in the reference), `seekr_nearest` (the k most correlated rows of every row: likewise) and
+`seekr_significant_pairs` (the pairs whose corrected p-value is at most alpha, without any N x N matrix: likewise), and
 `seekr_kmer_leiden` with the reference's flags (console_scripts.py:1033-1101) plus --edges.  Only the commands on the hot
 path are provided."""
 import argparse
@@ -91,6 +92,22 @@ Examples
 --------
     ten neighbours within one file:    seekr_nearest counts.csv -o nearest.csv
     three of b.npy for each of a.npy:  seekr_nearest a.npy b.npy -n 3 -o nearest.csv -bi
+"""
+
+SIGNIFICANT_PAIRS_DOC = """
+Description
+-----------
+The significantly similar pairs of rows of a k-mer count file, computed on an MI355X without the all-pairs matrix, the
+p-value matrix or the corrected matrix ever standing anywhere: r of every pair against a background (the similarities
+find_dist saved, or a fitted distribution with its parameters), the p-values corrected over all N (N - 1) / 2 pairs, and
+the pairs whose corrected p-value is at most alpha.  The output is a CSV with the columns row,col,r,p,p_adj, one line
+per pair (row before col), named by the labels of the count file or by indices for .npy input.  Methods: bonferroni,
+sidak, holm-sidak, holm, simes-hochberg, fdr_bh, fdr_by.
+
+Examples
+--------
+    against saved background similarities:   seekr_significant_pairs counts.csv -bg background.npy -o pairs.csv
+    against a fitted normal, Bonferroni:     seekr_significant_pairs counts.npy -bi -d norm -p 0.01 0.12 -m bonferroni -a 0.01 -o pairs.csv
 """
 
 _LOG2 = ["Log2.post", "Log2.pre", "Log2.none"]
@@ -281,6 +298,51 @@ def console_nearest():
     parser.add_argument("-bi", "--binary_input", action="store_true", help="The count files are .npy, not labelled CSV.")
     args = _parse_args_or_exit(parser)
     _run_nearest(args.counts1, args.counts2, int(args.neighbors), args.outfile, args.binary_input)
+
+
+def _read_background(path):
+    """A 1-D array of background similarities: a .npy file or a one-column CSV (what find_dist writes with
+    fit_model=False and an outputname)."""
+    if str(path).endswith(".npy"):
+        return np.asarray(np.load(path)).reshape(-1)
+    return np.loadtxt(path, delimiter=",", ndmin=1).reshape(-1)
+
+
+def _run_significant_pairs(counts, outfile, binary_input, background, dist, params, method, alpha):
+    import csv
+    from seekr_amd import significant
+    names = None
+    if binary_input:
+        counts = np.load(counts)
+    else:
+        counts, names = _read_labelled_csv(counts)
+    fitres = _read_background(background) if background is not None else [(dist, 0.0, tuple(float(v) for v in params))]
+    res = significant.significant_pairs(counts, fitres, method=method, alpha=alpha)
+    with open(outfile, "w", newline="") as f:
+        out = csv.writer(f, lineterminator="\n")
+        out.writerow(["row", "col", "r", "p", "p_adj"])
+        for i, j, r, p, q in zip(res.rows, res.cols, res.r, res.p, res.p_adj):
+            out.writerow([int(i) if names is None else names[int(i)], int(j) if names is None else names[int(j)], str(r), str(p),
+                          repr(float(q))])
+
+
+def console_significant_pairs():
+    parser = argparse.ArgumentParser(usage=SIGNIFICANT_PAIRS_DOC, formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    parser.add_argument("counts", help="Count file whose pairs of rows are tested.")
+    parser.add_argument("-bi", "--binary_input", action="store_true", help="The count file is .npy, not labelled CSV.")
+    parser.add_argument("-o", "--outfile", default="significant_pairs.csv", help="Where the list goes (CSV: row,col,r,p,p_adj).")
+    source = parser.add_mutually_exclusive_group(required=True)
+    source.add_argument("-bg", "--background", default=None,
+                        help="Background similarities: a .npy file or a one-column CSV (find_dist's output without a fit).")
+    source.add_argument("-d", "--distribution", default=None, help="Name of the fitted distribution (with -p).")
+    parser.add_argument("-p", "--params", nargs="+", default=None, help="Its parameters as find_dist lists them (shape, loc, scale).")
+    parser.add_argument("-m", "--method", default="fdr_bh", help="Correction method (statsmodels' multipletests names).")
+    parser.add_argument("-a", "--alpha", default=0.05, help="Pairs with a corrected p-value of at most this are listed.")
+    args = _parse_args_or_exit(parser)
+    if args.distribution is not None and not args.params:
+        parser.error("-d needs the parameters of the distribution: -p P [P ...]")
+    _run_significant_pairs(args.counts, args.outfile, args.binary_input, args.background, args.distribution, args.params,
+                           args.method, float(args.alpha))
 
 
 KMER_LEIDEN_DOC = """

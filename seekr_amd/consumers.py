@@ -10,6 +10,8 @@ it: keeping these reductions on the GPU avoids shipping an N x N m
     topk_rows / pearson_topk  —                  the k most correlated rows of every row; pearson_topk merges r block by
                                                  block into running lists (N x N never exists)
     adjust_pvalues        adj_pval.py:53-138     multipletests on the p-value matrix (symmetric: upper triangle)
+    adjust_pvalues_head   —                      the same for the smallest p-values of a longer list (seekr_amd.significant)
+    select_le / gather_index  —                  the positions of a vector with value <= bound, and a gather by them
 
 Every function takes and returns device matrices (`seekr_amd._lib.Matrix`); `*_host` helpers
 wrap host arrays for drop-in use.
@@ -351,4 +353,61 @@ def adjust_pvalues(p, method, alpha=0.05, symmetric=None):
     out = p.ctx.empty(p.rows, p.cols, adjust_out_dtype(name, p.dtype, symmetric))
     _lib.check(_lib.lib().skr_adjust_pvalues(p.ctx._h, p._h, ADJ_METHODS[name], C.c_double(float(alpha)),
                                              1 if symmetric else 0, out._h))
+    return out
+
+
+HEAD_METHODS = ("bonferroni", "sidak", "holm-sidak", "holm", "simes-hochberg", "fdr_bh", "fdr_by")
+HEAD_REFUSED = ("hommel", "fdr_tsbh", "fdr_tsbky", "fdr_gbs")
+
+
+def head_method(method):
+    """adjust_method(method) if the method can be corrected from the smallest p-values alone (HEAD_METHODS);
+    NotImplementedError naming the four that cannot (no device call)."""
+    name = adjust_method(method)
+    if name in HEAD_REFUSED:
+        raise NotImplementedError(
+            "{} cannot be corrected from the smallest p-values alone: {} depend on the tests above alpha or on a rejection "
+            "count that rescales alpha; use adjust_pvalues on the whole matrix".format(name, ", ".join(HEAD_REFUSED)))
+    return name
+
+
+def adjust_pvalues_head(p, ntests, method, alpha=0.05):
+    """The corrected values (1 x E float64 device vector) of the E smallest of `ntests` tests, given in any order in the
+    device vector p (float32 or float64): what adjust_pvalues(symmetric=True) gives those tests among all `ntests`, the
+    missing ones taken to be larger than every given one (skr_adjust_pvalues_head).  HEAD_METHODS only."""
+    name = head_method(method)
+    n = p.rows * p.cols
+    if int(ntests) < n:
+        raise ValueError("ntests ({}) is smaller than the {} p-values given".format(int(ntests), n))
+    if int(ntests) == 0:
+        raise ZeroDivisionError("float division by zero")
+    out = p.ctx.empty(1, n, np.float64)
+    if n:
+        _lib.check(_lib.lib().skr_adjust_pvalues_head(p.ctx._h, p._h, int(ntests), ADJ_METHODS[name], C.c_double(float(alpha)),
+                                                      out._h))
+    return out
+
+
+def select_le(values, bound):
+    """(index, count): the positions i of the device vector `values` (float32 or float64) with float64(values[i]) <= bound,
+    ascending, as the first `count` cells of a uint32 device vector (skr_select_le: count, then write); NaN never
+    passes.  index is None when nothing passes."""
+    ctx = values.ctx
+    count = C.c_int64(0)
+    if values.rows * values.cols == 0:
+        return None, 0
+    _lib.check(_lib.lib().skr_select_le(ctx._h, values._h, C.c_double(float(bound)), None, C.byref(count)))
+    n = count.value
+    if n == 0:
+        return None, 0
+    index = ctx.empty(1, n, np.uint32)
+    _lib.check(_lib.lib().skr_select_le(ctx._h, values._h, C.c_double(float(bound)), index._h, C.byref(count)))
+    return index, n
+
+
+def gather_index(src, index, count):
+    """1 x count device vector out[i] = src[index[i]] (src: uint32, float32 or float64 cells; index as select_le gives it)."""
+    out = src.ctx.empty(1, int(count), src.dtype)
+    if count:
+        _lib.check(_lib.lib().skr_gather_index(src.ctx._h, src._h, index._h, int(count), out._h))
     return out

@@ -11,6 +11,8 @@
 //                      the corrected value into the final layout
 //   elementwise_kernel bonferroni / sidak: no sort, one pass
 //   hommel_*           the O(n^2) definition in parallel (n <= 2^22)
+// skr_adjust_pvalues_head runs the same passes over the E smallest of ntests tests: Raw::ntests is the number of tests in
+// the formulas, Raw::n the entries that exist (seven methods: the values <= alpha need no more, DESIGN_PARITY.md)
 //
 // Every expression rounds as numpy evaluates the statsmodels source (this file is compiled with -ffp-contract=off); the
 // one deliberate difference is sidak's float32 power, which is evaluated in float64 and rounded once (numpy's float32
@@ -118,7 +120,8 @@ struct KeyPass {
 struct Raw {
     const void* keys;    // sorted keys (K of the dtype)
     const double* src;   // instead: a float64 array (the second scan of fdr_gbs, hommel's suffix max)
-    int64_t n;
+    int64_t n;           // entries of keys / src: the sorted positions that exist
+    int64_t ntests;      // the number of tests the formulas speak of (n, or more: skr_adjust_pvalues_head)
     int method;
     double cm;           // fdr_by's sum of 1/k
 };
@@ -128,11 +131,11 @@ template <typename T>
 __device__ __forceinline__ double raw_at(const Raw& r, int64_t i) {
     if (r.src) return r.src[i];
     const T s = value_of_key<T>(((const typename KeyOf<T>::K*)r.keys)[i]);
-    const double n = (double)r.n, ds = (double)s;
+    const double n = (double)r.ntests, ds = (double)s;
     switch (r.method) {
-        case SKR_ADJ_HOLM_SIDAK: return 1.0 - pow((double)((T)1 - s), (double)(r.n - i));
-        case SKR_ADJ_HOLM: return ds * (double)(r.n - i);
-        case SKR_ADJ_SIMES_HOCHBERG: return (double)(r.n - i) * ds;
+        case SKR_ADJ_HOLM_SIDAK: return 1.0 - pow((double)((T)1 - s), (double)(r.ntests - i));
+        case SKR_ADJ_HOLM: return ds * (double)(r.ntests - i);
+        case SKR_ADJ_SIMES_HOCHBERG: return (double)(r.ntests - i) * ds;
         case SKR_ADJ_FDR_BY: return ds / (((double)(i + 1) / n) / r.cm);
         case SKR_ADJ_FDR_GBS: return (n + 1.0 - (double)(i + 1)) / (double)(i + 1) * ds / (double)((T)1 - s);
         default: return ds / ((double)(i + 1) / n);  // fdr_bh and the two-stage methods
@@ -436,7 +439,8 @@ struct Plan {
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-Plan plan_for(const skr_ctx* ctx, int64_t n, size_t key_bytes, bool hommel) {
+// harmonic_n: the length fdr_by's harmonic sum runs over (the number of tests)
+Plan plan_for(const skr_ctx* ctx, int64_t n, size_t key_bytes, bool hommel, int64_t harmonic_n) {
     Plan p;
     p.n = n;
     p.sort = skr_radix::plan_chunks(ctx, n);
@@ -455,7 +459,7 @@ Plan plan_for(const skr_ctx* ctx, int64_t n, size_t key_bytes, bool hommel) {
     p.off_scan = off;
     off = align256(off + (p.sort.scan_words + 16) * 8);
     p.off_acc = off;  // scan aggregates, or fdr_by's buffer sums
-    off = align256(off + (size_t)std::max<int64_t>(p.acc_blocks, (n + 8191) / 8192 + 1) * 8);
+    off = align256(off + (size_t)std::max<int64_t>(p.acc_blocks, (harmonic_n + 8191) / 8192 + 1) * 8);
     p.off_hommel = off;
     if (hommel) off = align256(off + (size_t)(n + 1) * 8 * 2);
     p.bytes = off;
@@ -529,14 +533,18 @@ int running(skr_ctx* ctx, const Plan& plan, char* base, const Raw& raw, bool is_
     return SKR_OK;
 }
 
+// head_ntests > 0 (skr_adjust_pvalues_head): p holds the n smallest of head_ntests tests; every formula takes
+// head_ntests as the number of tests, every array has n entries, and out is float64 as for `upper`
 template <typename T>
-int adjust_typed(skr_ctx* ctx, const skr_mat* p, int method, double alpha, bool upper, skr_mat* out) {
+int adjust_typed(skr_ctx* ctx, const skr_mat* p, int method, double alpha, bool upper, skr_mat* out, int64_t head_ntests = 0) {
     using K = typename KeyOf<T>::K;
     const int64_t rows = p->rows, cols = p->cols, cells = rows * cols;
     const int64_t n = upper ? rows * (rows - 1) / 2 : cells;
-    if (n == 0) return skr_set_error(SKR_ERR_ZERODIV, "float division by zero");  // 1./ntests in multipletests
+    const int64_t ntests = head_ntests > 0 ? head_ntests : n;
+    if (ntests == 0) return skr_set_error(SKR_ERR_ZERODIV, "float division by zero");  // 1./ntests in multipletests
+    if (n == 0) return SKR_OK;  // a head without tests: nothing to write
     const bool keep_dtype = method == SKR_ADJ_BONFERRONI || method == SKR_ADJ_SIDAK || method == SKR_ADJ_HOMMEL;
-    const int out_dtype = upper || !keep_dtype ? SKR_F64 : p->dtype;
+    const int out_dtype = upper || head_ntests > 0 || !keep_dtype ? SKR_F64 : p->dtype;
     SKR_REQUIRE(out->rows == rows && out->cols == cols && out->dtype == out_dtype,
                 "out must be a [%lld, %lld] %s matrix", (long long)rows, (long long)cols,
                 out_dtype == SKR_F64 ? "float64" : "float32");
@@ -549,18 +557,18 @@ int adjust_typed(skr_ctx* ctx, const skr_mat* p, int method, double alpha, bool 
         const int sidak = method == SKR_ADJ_SIDAK;
         if (upper)
             hipLaunchKernelGGL((elementwise_kernel<T, double, true>), dim3(skr_grid(ctx, cells)), dim3(256), 0, ctx->stream, pd,
-                               cols, cells, n, sidak, (double*)out->data);
+                               cols, cells, ntests, sidak, (double*)out->data);
         else if (out_dtype == SKR_F64)
             hipLaunchKernelGGL((elementwise_kernel<T, double, false>), dim3(skr_grid(ctx, cells)), dim3(256), 0, ctx->stream, pd,
-                               cols, cells, n, sidak, (double*)out->data);
+                               cols, cells, ntests, sidak, (double*)out->data);
         else
             hipLaunchKernelGGL((elementwise_kernel<T, T, false>), dim3(skr_grid(ctx, cells)), dim3(256), 0, ctx->stream, pd,
-                               cols, cells, n, sidak, (T*)out->data);
+                               cols, cells, ntests, sidak, (T*)out->data);
         SKR_HIP(hipGetLastError());
         return SKR_OK;
     }
 
-    const Plan plan = plan_for(ctx, n, sizeof(K), method == SKR_ADJ_HOMMEL);
+    const Plan plan = plan_for(ctx, n, sizeof(K), method == SKR_ADJ_HOMMEL, method == SKR_ADJ_FDR_BY ? ntests : n);
     void* ws = nullptr;
     SKR_TRY(workspace_for(ctx, plan, &ws));
     char* base = (char*)ws;
@@ -586,7 +594,7 @@ int adjust_typed(skr_ctx* ctx, const skr_mat* p, int method, double alpha, bool 
     Fin fin{0, 1.0, 1.0};
     {
         SkrProfScope prof(ctx, "adjust_scan");
-        Raw r{sorted, nullptr, n, method, 0.0};
+        Raw r{sorted, nullptr, n, ntests, method, 0.0};
         if (method == SKR_ADJ_HOMMEL) {
             double* cim = (double*)(base + plan.off_hommel);
             double* suf = cim + (n + 1);
@@ -595,7 +603,7 @@ int adjust_typed(skr_ctx* ctx, const skr_mat* p, int method, double alpha, bool 
                                    dim3(256), 0, ctx->stream, sorted, n, cim);
                 SKR_HIP(hipGetLastError());
                 // suf[m] for m in [2, n]: the running max from the end of cim[2..n]
-                const Raw rs{nullptr, cim + 2, n - 1, method, 0.0};
+                const Raw rs{nullptr, cim + 2, n - 1, n - 1, method, 0.0};
                 SKR_TRY(running<T>(ctx, plan, base, rs, true, true, suf + 2));
             }
             hipLaunchKernelGGL(hommel_cells_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, sorted, n,
@@ -605,8 +613,8 @@ int adjust_typed(skr_ctx* ctx, const skr_mat* p, int method, double alpha, bool 
             const bool fwd_max = method == SKR_ADJ_HOLM || method == SKR_ADJ_HOLM_SIDAK || method == SKR_ADJ_FDR_GBS;
             if (method == SKR_ADJ_FDR_BY) {
                 double* sums = (double*)(base + plan.off_acc);
-                const int64_t nb = (n + 8191) / 8192;
-                hipLaunchKernelGGL(harmonic_buffers_kernel, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, ctx->stream, n, sums);
+                const int64_t nb = (ntests + 8191) / 8192;
+                hipLaunchKernelGGL(harmonic_buffers_kernel, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, ctx->stream, ntests, sums);
                 SKR_HIP(hipGetLastError());
                 double* host = (double*)malloc((size_t)nb * 8);
                 if (!host) return skr_set_error(SKR_ERR_NOMEM, "host buffer of %lld doubles", (long long)nb);
@@ -620,7 +628,7 @@ int adjust_typed(skr_ctx* ctx, const skr_mat* p, int method, double alpha, bool 
             }
             if (method == SKR_ADJ_FDR_GBS) {  // running max, then a running min from the end of that
                 SKR_TRY(running<T>(ctx, plan, base, r, true, false, c));
-                const Raw r2{nullptr, c, n, method, 0.0};
+                const Raw r2{nullptr, c, n, n, method, 0.0};
                 SKR_TRY(running<T>(ctx, plan, base, r2, false, true, c));
             } else {
                 SKR_TRY(running<T>(ctx, plan, base, r, fwd_max, !fwd_max, c));
@@ -705,4 +713,23 @@ extern "C" int skr_adjust_pvalues(skr_ctx* ctx, const skr_mat* p, int method, do
     SKR_TRY(skr_activate(ctx));
     if (p->dtype == SKR_F64) return adjust_typed<double>(ctx, p, method, alpha, upper_only != 0, out);
     return adjust_typed<float>(ctx, p, method, alpha, upper_only != 0, out);
+}
+
+extern "C" int skr_adjust_pvalues_head(skr_ctx* ctx, const skr_mat* p, int64_t ntests, int method, double alpha, skr_mat* out) {
+    SKR_REQUIRE(ctx && p && out && p->ctx == ctx && out->ctx == ctx, "NULL argument or foreign ctx");
+    SKR_REQUIRE(p->dtype == SKR_F32 || p->dtype == SKR_F64, "float32 or float64 p-values");
+    SKR_REQUIRE(method >= SKR_ADJ_BONFERRONI && method <= SKR_ADJ_FDR_GBS, "method not recognized");
+    static const char* const kNames[] = {"bonferroni", "sidak", "holm-sidak", "holm", "simes-hochberg", "hommel", "fdr_bh",
+                                         "fdr_by", "fdr_tsbh", "fdr_tsbky", "fdr_gbs"};
+    if (method == SKR_ADJ_HOMMEL || method == SKR_ADJ_FDR_TSBH || method == SKR_ADJ_FDR_TSBKY || method == SKR_ADJ_FDR_GBS)
+        return skr_set_error(SKR_ERR_UNSUPPORTED,
+                             "%s cannot be corrected from the smallest p-values alone: its values depend on the tests "
+                             "that are left out", kNames[method]);
+    const int64_t given = p->rows * p->cols;
+    SKR_REQUIRE(ntests >= given, "ntests (%lld) is smaller than the %lld p-values given", (long long)ntests, (long long)given);
+    SKR_REQUIRE(out->data != p->data || given == 0, "out must not alias p");
+    SKR_TRY(skr_activate(ctx));
+    if (ntests == 0) return skr_set_error(SKR_ERR_ZERODIV, "float division by zero");
+    if (p->dtype == SKR_F64) return adjust_typed<double>(ctx, p, method, alpha, false, out, ntests);
+    return adjust_typed<float>(ctx, p, method, alpha, false, out, ntests);
 }

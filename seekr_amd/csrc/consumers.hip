@@ -305,6 +305,61 @@ __global__ __launch_bounds__(256) void parametric_p_kernel(const float* __restri
     if (failed && d.not_converged) atomicOr(d.not_converged, 1);  // gamma / chi2 only: the others never set it
 }
 
+// ---- stable selection: the positions i with (double)values[i] <= bound, ascending (NaN never passes) ----------
+// Tiles of 256 values, a workgroup walks tiles blockIdx.x, blockIdx.x + gridDim.x, ...: counts[tile] first, then (after
+// the exclusive scan of the counts) the positions, a value's place inside its tile from wave ballots as in
+// edges_fill_kernel.
+constexpr int kSelectTile = 256;
+
+template <typename T>
+__global__ __launch_bounds__(kSelectTile) void select_count_kernel(const T* __restrict__ v, int64_t n, double bound,
+                                                                   int64_t tiles, unsigned long long* __restrict__ counts) {
+    __shared__ unsigned red[kSelectTile / 64];
+    for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const int64_t i = t * kSelectTile + threadIdx.x;
+        const bool keep = i < n && (double)v[i] <= bound;
+        const unsigned long long mask = __ballot(keep);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = (unsigned)__popcll(mask);
+        __syncthreads();
+        if (threadIdx.x == 0) counts[t] = (unsigned long long)red[0] + red[1] + red[2] + red[3];
+        __syncthreads();
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kSelectTile) void select_fill_kernel(const T* __restrict__ v, int64_t n, double bound,
+                                                                  int64_t tiles, const unsigned long long* __restrict__ offsets,
+                                                                  uint32_t* __restrict__ out) {
+    __shared__ unsigned wave_n[kSelectTile / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const int64_t i = t * kSelectTile + threadIdx.x;
+        const bool keep = i < n && (double)v[i] <= bound;
+        const unsigned long long mask = __ballot(keep);
+        if (lane == 0) wave_n[wave] = (unsigned)__popcll(mask);
+        __syncthreads();
+        unsigned before = 0;
+#pragma unroll
+        for (int w = 0; w < kSelectTile / 64; w++)
+            if (w < wave) before += wave_n[w];
+        if (keep) out[offsets[t] + before + __popcll(mask & ((1ull << lane) - 1))] = (uint32_t)i;
+        __syncthreads();
+    }
+}
+
+// out[i] = src[index[i]], 4- or 8-byte cells; an index outside src raises the flag and writes nothing
+template <typename W>
+__global__ __launch_bounds__(256) void gather_index_kernel(const W* __restrict__ src, int64_t n_src, const uint32_t* __restrict__ index,
+                                                           int64_t count, W* __restrict__ out, int* __restrict__ bad) {
+    bool any_bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256) {
+        const int64_t j = index[i];
+        if (j < n_src) out[i] = src[j];
+        else any_bad = true;
+    }
+    if (any_bad) atomicOr(bad, 1);
+}
+
 }  // namespace
 
 extern "C" int skr_threshold_zero_diag(skr_ctx* ctx, skr_mat* r, float cutoff, int64_t diag_col0) {
@@ -423,6 +478,85 @@ extern "C" int skr_edges(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t 
     hipLaunchKernelGGL(edges_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream, a, counts, (uint32_t*)out_rows->data,
                        (uint32_t*)out_cols->data, (float*)out_vals->data);
     SKR_HIP(hipGetLastError());
+    return SKR_OK;
+}
+
+extern "C" int skr_select_le(skr_ctx* ctx, const skr_mat* values, double bound, skr_mat* out_index, int64_t* count) {
+    SKR_REQUIRE(ctx && values && count && values->ctx == ctx, "need a vector of this ctx and a count");
+    SKR_REQUIRE(values->dtype == SKR_F32 || values->dtype == SKR_F64, "float32 or float64 values");
+    SKR_REQUIRE(!out_index || (out_index->ctx == ctx && out_index->dtype == SKR_U32), "out_index is a U32 vector of this ctx");
+    const int64_t n = values->rows * values->cols;
+    SKR_REQUIRE(n <= 0xffffffffLL, "positions must fit 32 bits");
+    SKR_TRY(skr_activate(ctx));
+    *count = 0;
+    if (n == 0) return SKR_OK;
+    const int64_t tiles = (n + kSelectTile - 1) / kSelectTile;
+    void* ws = nullptr;
+    // per-tile counts and a zero behind them: scanned in place, offsets[tiles] is the total.  Then the scan's scratch.
+    SKR_TRY(skr_ctx_workspace(ctx, ((size_t)tiles + 1 + skr_radix::scan_scratch_words(tiles + 1)) * 8, &ws));
+    unsigned long long* counts = (unsigned long long*)ws;
+    unsigned long long* total = counts + tiles;
+    SKR_HIP(hipMemsetAsync(total, 0, 8, ctx->stream));
+    const dim3 grid((unsigned)std::min<int64_t>(tiles, (int64_t)ctx->num_cu * 16));
+    const bool f64 = values->dtype == SKR_F64;
+    {
+        SkrProfScope prof(ctx, "select_count");
+        if (f64)
+            hipLaunchKernelGGL(select_count_kernel<double>, grid, dim3(kSelectTile), 0, ctx->stream, (const double*)values->data, n,
+                               bound, tiles, counts);
+        else
+            hipLaunchKernelGGL(select_count_kernel<float>, grid, dim3(kSelectTile), 0, ctx->stream, (const float*)values->data, n,
+                               bound, tiles, counts);
+        SKR_HIP(hipGetLastError());
+    }
+    SKR_TRY(skr_radix::exclusive_scan<unsigned long long>(ctx, counts, tiles + 1, total + 1));
+    unsigned long long h_total = 0;
+    SKR_HIP(hipMemcpyAsync(&h_total, total, 8, hipMemcpyDeviceToHost, ctx->stream));
+    SKR_HIP(hipStreamSynchronize(ctx->stream));
+    *count = (int64_t)h_total;
+    if (!out_index || h_total == 0) return SKR_OK;
+    const int64_t cap = out_index->rows * out_index->cols;
+    SKR_REQUIRE((int64_t)h_total <= cap, "%lld positions do not fit an output of %lld cells", (long long)h_total, (long long)cap);
+    SkrProfScope prof(ctx, "select_fill");
+    if (f64)
+        hipLaunchKernelGGL(select_fill_kernel<double>, grid, dim3(kSelectTile), 0, ctx->stream, (const double*)values->data, n, bound,
+                           tiles, counts, (uint32_t*)out_index->data);
+    else
+        hipLaunchKernelGGL(select_fill_kernel<float>, grid, dim3(kSelectTile), 0, ctx->stream, (const float*)values->data, n, bound,
+                           tiles, counts, (uint32_t*)out_index->data);
+    SKR_HIP(hipGetLastError());
+    return SKR_OK;
+}
+
+extern "C" int skr_gather_index(skr_ctx* ctx, const skr_mat* src, const skr_mat* index, int64_t count, skr_mat* out) {
+    SKR_REQUIRE(ctx && src && index && out, "NULL argument");
+    SKR_REQUIRE(src->ctx == ctx && index->ctx == ctx && out->ctx == ctx, "foreign ctx");
+    SKR_REQUIRE(index->dtype == SKR_U32 && out->dtype == src->dtype, "index is U32, out has src's dtype");
+    SKR_REQUIRE(count >= 0 && count <= index->rows * index->cols && count <= out->rows * out->cols,
+                "count exceeds the index list or the output");
+    SKR_REQUIRE(out->data != src->data || count == 0, "out must not alias src");
+    SKR_TRY(skr_activate(ctx));
+    if (count == 0) return SKR_OK;
+    void* ws = nullptr;
+    SKR_TRY(skr_ctx_workspace(ctx, 64, &ws));
+    int* bad = (int*)ws;
+    SKR_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
+    const int64_t n_src = src->rows * src->cols;
+    {
+        SkrProfScope prof(ctx, "gather_index");
+        if (src->elem() == 8)
+            hipLaunchKernelGGL(gather_index_kernel<unsigned long long>, dim3(skr_grid(ctx, count)), dim3(256), 0, ctx->stream,
+                               (const unsigned long long*)src->data, n_src, (const uint32_t*)index->data, count,
+                               (unsigned long long*)out->data, bad);
+        else
+            hipLaunchKernelGGL(gather_index_kernel<uint32_t>, dim3(skr_grid(ctx, count)), dim3(256), 0, ctx->stream,
+                               (const uint32_t*)src->data, n_src, (const uint32_t*)index->data, count, (uint32_t*)out->data, bad);
+        SKR_HIP(hipGetLastError());
+    }
+    int h_bad = 0;
+    SKR_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    SKR_HIP(hipStreamSynchronize(ctx->stream));
+    SKR_REQUIRE(!h_bad, "an index lies outside the %lld cells of src", (long long)n_src);
     return SKR_OK;
 }
 

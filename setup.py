@@ -20,6 +20,8 @@ setup(
             "seekr_domain_pearson = seekr_amd.console_scripts:console_domain_pearson",
             # the k most correlated rows of every row, without the all-pairs matrix (no counterpart either)
             "seekr_nearest = seekr_amd.console_scripts:console_nearest",
+            # the pairs with a corrected p-value <= alpha, without r, p or the corrected matrix (no counterpart either)
+            "seekr_significant_pairs = seekr_amd.console_scripts:console_significant_pairs",
             "seekr_kmer_leiden = seekr_amd.console_scripts:console_kmer_leiden",
         ]
     },
