@@ -452,6 +452,26 @@ int skr_select_le(skr_ctx* ctx, const skr_mat* values, double bound, skr_mat* ou
  * skr_select_le writes it), out of src's dtype; an index outside src: SKR_ERR_INVALID.                              */
 int skr_gather_index(skr_ctx* ctx, const skr_mat* src, const skr_mat* index, int64_t count, skr_mat* out);
 
+/* The cells of the float32 block r[0:nrows, col_begin:col_end] with !(v < cutoff), appended to a list on the device:
+ * NaN is kept (numpy's mask keeps it), a cell equal to the cutoff is kept, and there is no zero rule and no diagonal
+ * rule — the block is a query x target matrix in which the cell (i, i) is a test like any other (skr_edges is the
+ * graph's rule).  *count receives their number, *saw_nan (may be NULL) whether a selected value is NaN.  With out_rows /
+ * out_cols (SKR_U32) and out_vals (SKR_F32) non-NULL the triplets (row_global0 + i, col_global0 + j, v), j = r's own
+ * column index, are written at cells out_offset ... out_offset + *count - 1 in row-major order — np.nonzero order of
+ * the mask over the block; the same input gives the same bytes.  If out_offset + *count exceeds the capacity of any
+ * output nothing is written and the call still returns SKR_OK with the count: the caller grows its buffers and calls
+ * again (the contract of skr_pearson_gemm_edges).  With all three NULL only the count and the flag are made.
+ * The work is cut into tiles of one row x one segment of 1 024 columns (segments start at a 16-byte boundary of the
+ * row's memory, so a row has up to ceil((width + 3) / 1 024) of them): a 3 x 65 536 block and an 8 192 x 300 block both
+ * spread over the device.  The block is read twice: counts per tile, their exclusive scan, then the fill. */
+int skr_select_cells_ge(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t col_begin, int64_t col_end,
+                        int64_t row_global0, int64_t col_global0, float cutoff, skr_mat* out_rows, skr_mat* out_cols,
+                        skr_mat* out_vals, int64_t out_offset, int64_t* count, int* saw_nan);
+/* dst[dst_off + i] = src[src_off + i] for i < count, on the ctx's stream: two device vectors of the same dtype (SKR_U32,
+ * SKR_F32 or SKR_F64), cells counted row-major.  A range outside either vector, or overlapping ranges of one
+ * allocation: SKR_ERR_INVALID.                                                                                     */
+int skr_vec_copy(skr_ctx* ctx, const skr_mat* src, int64_t src_off, skr_mat* dst, int64_t dst_off, int64_t count);
+
 /* The non-zero cells that kmer_leiden.py:94-96 leaves in a block of r, as an edge list and
  * without writing the zeros: cells of r[0:nrows, col_begin:col_end] with !(v < cutoff) (NaN
  * stays, like numpy's mask), v != 0 and global row != global column, where global row =

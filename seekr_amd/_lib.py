@@ -122,6 +122,9 @@ SIGNATURES = {
     "skr_adjust_pvalues_head": (_int, [_p, _p, _i64, _int, C.c_double, _p]),
     "skr_select_le": (_int, [_p, _p, C.c_double, _p, C.POINTER(_i64)]),
     "skr_gather_index": (_int, [_p, _p, _p, _i64, _p]),
+    "skr_select_cells_ge": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, C.c_float, _p, _p, _p, _i64, C.POINTER(_i64),
+                                  C.POINTER(_int)]),
+    "skr_vec_copy": (_int, [_p, _p, _i64, _p, _i64, _i64]),
     "skr_edges": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, C.c_float, _int, _p, _p, _p, C.POINTER(_i64)]),
     "skr_pearson_gemm_edges": (_int, [_p, _p, _p, _p, _i64, _i64, C.c_float, _int, _p, _p, _p, C.POINTER(_i64)]),
     "skr_pearson_gemm_edges_needs_scratch": (_int, [_p, _p, _p, C.POINTER(_int)]),
@@ -1120,6 +1123,9 @@ TOPK_MERGE_KMAX = 256    # largest k of skr_topk_merge_rows
 TOPK_MERGE_CAP = 1792    # candidates its buffer holds
 TOPK_MERGE_STEP = 1024   # cells per sweep step: buffer and list are sorted when more than CAP - STEP candidates wait
 TOPK_PAD_IDX, TOPK_PAD_BITS = 0xFFFFFFFF, 0x7FC00000  # an unfilled slot
+# columns per tile of skr_select_cells_ge (csrc/cells.hip: kCellSegment): a row's segments start at the 16-byte boundary
+# at or below its first selected cell, so widths around a multiple of this walk the tile edges
+SELECT_CELLS_SEGMENT = 1024
 
 
 def topk_merge_limits():

@@ -102,12 +102,31 @@ p-value matrix or the corrected matrix ever standing anywhere: r of every pair a
 find_dist saved, or a fitted distribution with its parameters), the p-values corrected over all N (N - 1) / 2 pairs, and
 the pairs whose corrected p-value is at most alpha.  The output is a CSV with the columns row,col,r,p,p_adj, one line
 per pair (row before col), named by the labels of the count file or by indices for .npy input.  Methods: bonferroni,
-sidak, holm-sidak, holm, simes-hochberg, fdr_bh, fdr_by.
+sidak, holm-sidak, holm, simes-hochberg, fdr_bh, fdr_by.  With a second count file the rows of the first are tested
+against the rows of the second (find_pval's two-file form): N1 x N2 tests, every cell one of them, `row` named from
+the first file and `col` from the second.
 
 Examples
 --------
     against saved background similarities:   seekr_significant_pairs counts.csv -bg background.npy -o pairs.csv
     against a fitted normal, Bonferroni:     seekr_significant_pairs counts.npy -bi -d norm -p 0.01 0.12 -m bonferroni -a 0.01 -o pairs.csv
+    queries against a transcriptome:         seekr_significant_pairs queries.csv transcripts.csv -bg background.npy -o pairs.csv
+"""
+
+DOMAIN_SIGNIFICANT_DOC = """
+Description
+-----------
+The sliding windows of the target sequences that each query is significantly similar to, computed on an MI355X without
+the query x window matrix ever leaving the device: r of every query against every window (as seekr_domain_pearson
+computes it), its p-value against a background (saved similarities, or a fitted distribution with its parameters),
+the p-values corrected over all queries x windows tests, and the cells whose corrected p-value is at most alpha.  The
+output is a CSV with the columns query,header,start,end,r,p,p_adj, one line per significant (query, window) cell in
+that order.  Methods: bonferroni, sidak, holm-sidak, holm, simes-hochberg, fdr_bh, fdr_by.
+
+Examples
+--------
+    seekr_domain_significant query.fa target.fa mean.npy std.npy -k 4 -w 500 -s 50 -bg background.npy -o domains.csv
+    seekr_domain_significant query.fa target.fa mean.npy std.npy -d norm -p 0.0 0.07 -m bonferroni -a 0.01 -o domains.csv
 """
 
 _LOG2 = ["Log2.post", "Log2.pre", "Log2.none"]
@@ -308,41 +327,89 @@ def _read_background(path):
     return np.loadtxt(path, delimiter=",", ndmin=1).reshape(-1)
 
 
-def _run_significant_pairs(counts, outfile, binary_input, background, dist, params, method, alpha):
-    import csv
-    from seekr_amd import significant
-    names = None
-    if binary_input:
-        counts = np.load(counts)
-    else:
-        counts, names = _read_labelled_csv(counts)
-    fitres = _read_background(background) if background is not None else [(dist, 0.0, tuple(float(v) for v in params))]
-    res = significant.significant_pairs(counts, fitres, method=method, alpha=alpha)
-    with open(outfile, "w", newline="") as f:
-        out = csv.writer(f, lineterminator="\n")
-        out.writerow(["row", "col", "r", "p", "p_adj"])
-        for i, j, r, p, q in zip(res.rows, res.cols, res.r, res.p, res.p_adj):
-            out.writerow([int(i) if names is None else names[int(i)], int(j) if names is None else names[int(j)], str(r), str(p),
-                          repr(float(q))])
+def _fitres(background, dist, params):
+    return _read_background(background) if background is not None else [(dist, 0.0, tuple(float(v) for v in params))]
 
 
-def console_significant_pairs():
-    parser = argparse.ArgumentParser(usage=SIGNIFICANT_PAIRS_DOC, formatter_class=argparse.ArgumentDefaultsHelpFormatter)
-    parser.add_argument("counts", help="Count file whose pairs of rows are tested.")
-    parser.add_argument("-bi", "--binary_input", action="store_true", help="The count file is .npy, not labelled CSV.")
-    parser.add_argument("-o", "--outfile", default="significant_pairs.csv", help="Where the list goes (CSV: row,col,r,p,p_adj).")
+def _add_significance_arguments(parser, what):
+    """-bg | -d -p, -m and -a: the background, the correction method and alpha of the significance commands."""
     source = parser.add_mutually_exclusive_group(required=True)
     source.add_argument("-bg", "--background", default=None,
                         help="Background similarities: a .npy file or a one-column CSV (find_dist's output without a fit).")
     source.add_argument("-d", "--distribution", default=None, help="Name of the fitted distribution (with -p).")
     parser.add_argument("-p", "--params", nargs="+", default=None, help="Its parameters as find_dist lists them (shape, loc, scale).")
     parser.add_argument("-m", "--method", default="fdr_bh", help="Correction method (statsmodels' multipletests names).")
-    parser.add_argument("-a", "--alpha", default=0.05, help="Pairs with a corrected p-value of at most this are listed.")
+    parser.add_argument("-a", "--alpha", default=0.05, help="%s with a corrected p-value of at most this are listed." % what)
+
+
+def _run_significant_pairs(counts, outfile, binary_input, background, dist, params, method, alpha, counts2=None):
+    import csv
+    from seekr_amd import significant
+    names = names2 = None
+    if binary_input:
+        counts = np.load(counts)
+        counts2 = None if counts2 is None else np.load(counts2)
+    else:
+        counts, names = _read_labelled_csv(counts)
+        counts2, names2 = (None, names) if counts2 is None else _read_labelled_csv(counts2)
+    res = significant.significant_pairs(counts, _fitres(background, dist, params), method=method, alpha=alpha, counts2=counts2)
+    with open(outfile, "w", newline="") as f:
+        out = csv.writer(f, lineterminator="\n")
+        out.writerow(["row", "col", "r", "p", "p_adj"])
+        for i, j, r, p, q in zip(res.rows, res.cols, res.r, res.p, res.p_adj):
+            out.writerow([int(i) if names is None else names[int(i)], int(j) if names2 is None else names2[int(j)], str(r), str(p),
+                          repr(float(q))])
+
+
+def console_significant_pairs():
+    parser = argparse.ArgumentParser(usage=SIGNIFICANT_PAIRS_DOC, formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    parser.add_argument("counts", help="Count file whose pairs of rows are tested.")
+    parser.add_argument("counts2", nargs="?", default=None,
+                        help="Count file whose rows those of `counts` are tested against (default: counts against itself).")
+    parser.add_argument("-bi", "--binary_input", action="store_true", help="The count files are .npy, not labelled CSV.")
+    parser.add_argument("-o", "--outfile", default="significant_pairs.csv", help="Where the list goes (CSV: row,col,r,p,p_adj).")
+    _add_significance_arguments(parser, "Pairs")
     args = _parse_args_or_exit(parser)
     if args.distribution is not None and not args.params:
         parser.error("-d needs the parameters of the distribution: -p P [P ...]")
     _run_significant_pairs(args.counts, args.outfile, args.binary_input, args.background, args.distribution, args.params,
-                           args.method, float(args.alpha))
+                           args.method, float(args.alpha), args.counts2)
+
+
+def _run_domain_significant(query, target, mean, std, kmer, window, slide, log2, outfile, background, dist, params, method,
+                            alpha):
+    import csv
+    from seekr_amd import windows
+    frame = windows.domain_significant(query, target, kmer, window, slide, mean, std, _fitres(background, dist, params),
+                                       method=method, alpha=alpha, log2=log2)
+    with open(outfile, "w", newline="") as f:
+        out = csv.writer(f, lineterminator="\n")
+        out.writerow(["query", "header", "start", "end", "r", "p", "p_adj"])
+        for q, h, s, e, r, p, a in zip(frame["query"], frame["header"], frame["start"], frame["end"], frame["r"], frame["p"],
+                                       frame["p_adj"]):
+            out.writerow([int(q), h, int(s), int(e), str(np.float32(r)), str(np.float32(p)), repr(float(a))])
+
+
+def console_domain_significant():
+    parser = argparse.ArgumentParser(usage=DOMAIN_SIGNIFICANT_DOC, formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    parser.add_argument("query", help="FASTA file with the query sequences.")
+    parser.add_argument("target", help="FASTA file with the target sequences; their sliding windows are tested.")
+    parser.add_argument("mean", help="Stored mean vector (.npy) both sides are centred with.")
+    parser.add_argument("std", help="Stored std vector (.npy) both sides are scaled with.")
+    parser.add_argument("-k", "--kmer", default=6, help="k, the word length (4^k columns; up to 7).")
+    parser.add_argument("-w", "--window", default=1000, help="Letters per window.")
+    parser.add_argument("-s", "--slide", default=100, help="Letters between the starts of two windows (at most the window).")
+    parser.add_argument("-l", "--log2", default="Log2.post", choices=_LOG2,
+                        help="log2 before the column statistics (pre), after them (post), or not at all (none).")
+    parser.add_argument("-o", "--outfile", default="domain_significant.csv",
+                        help="Where the list goes (CSV: query,header,start,end,r,p,p_adj).")
+    _add_significance_arguments(parser, "Windows")
+    args = _parse_args_or_exit(parser)
+    if args.distribution is not None and not args.params:
+        parser.error("-d needs the parameters of the distribution: -p P [P ...]")
+    _run_domain_significant(args.query, args.target, args.mean, args.std, int(args.kmer), int(args.window), int(args.slide),
+                            args.log2, args.outfile, args.background, args.distribution, args.params, args.method,
+                            float(args.alpha))
 
 
 KMER_LEIDEN_DOC = """

@@ -108,9 +108,10 @@ def empirical_pvalues_host(sim, fitres):
     return empirical_pvalues(ctx.from_numpy(sim), fitres).to_numpy()
 
 
-def edges(r, cutoff, nrows=None, col_begin=0, col_end=None, row_global0=0, col_global0=0, upper_only=False):
+def edges(r, cutoff, nrows=None, col_begin=0, col_end=None, row_global0=0, col_global0=0, upper_only=False, into=None):
     """(rows, cols, vals) numpy arrays (uint32, uint32, float32): the cells of the device block
-    r[0:nrows, col_begin:col_end] that kmer_leiden.py:94-96 leaves non-zero, in np.nonzero order."""
+    r[0:nrows, col_begin:col_end] that kmer_leiden.py:94-96 leaves non-zero, in np.nonzero order.  into: a CellList the
+    outputs are appended to on the device instead; the number of edges is returned."""
     ctx = r.ctx
     nrows = r.rows if nrows is None else nrows
     col_end = r.cols if col_end is None else col_end
@@ -120,10 +121,14 @@ def edges(r, cutoff, nrows=None, col_begin=0, col_end=None, row_global0=0, col_g
     _lib.check(_lib.lib().skr_edges(*args, None, None, None, C.byref(count)))
     n = count.value
     if n == 0:
-        return np.empty(0, np.uint32), np.empty(0, np.uint32), np.empty(0, np.float32)
+        return 0 if into is not None else (np.empty(0, np.uint32), np.empty(0, np.uint32), np.empty(0, np.float32))
     out_r, out_c, out_v = ctx.empty(1, n, np.uint32), ctx.empty(1, n, np.uint32), ctx.empty(1, n, np.float32)
     _lib.check(_lib.lib().skr_edges(*args, out_r._h, out_c._h, out_v._h, C.byref(count)))
-    res = out_r.to_numpy().reshape(-1), out_c.to_numpy().reshape(-1), out_v.to_numpy().reshape(-1)
+    if into is not None:
+        into.append_from(out_r, out_c, out_v, n)
+        res = n
+    else:
+        res = out_r.to_numpy().reshape(-1), out_c.to_numpy().reshape(-1), out_v.to_numpy().reshape(-1)
     for m in (out_r, out_c, out_v):
         m.free()
     return res
@@ -149,11 +154,12 @@ class FusedEdges:
                          self.ctx.empty(self.cap, 1, np.float32))
         return self._out
 
-    def block(self, a, b, cutoff, row_global0=0, col_global0=0, upper_only=False, scratch=None, retry=True):
+    def block(self, a, b, cutoff, row_global0=0, col_global0=0, upper_only=False, scratch=None, retry=True, into=None):
         """(rows, cols, vals) of the block a b^T / K, global indices, np.nonzero order.  `scratch`: a float32 matrix of at
         least [a.rows, b.rows] for rows of more than 4 096 columns (allocated and kept here when not given).  The list
         buffers start at 2e-3 entries per cell; a block with more edges is run again with room (retry=True) or reported
-        as None (retry=False: the caller has a cheaper way for lists that dense)."""
+        as None (retry=False: the caller has a cheaper way for lists that dense).  into: a CellList the filled prefix
+        of the buffers is appended to on the device; the number of edges is returned and nothing crosses PCIe."""
         ctx = self.ctx
         # more than one accumulator restart per row?  the library's own rule, knob included (ADVICE r3: not re-derived here)
         needs = C.c_int(0)
@@ -178,6 +184,9 @@ class FusedEdges:
             if not retry:
                 return None
             self.cap = int(n * 1.25) + 1024  # more edges than the buffers hold: once more with room
+        if into is not None:
+            into.append_from(o_r, o_c, o_v, n)
+            return n
         if n == 0:
             return np.empty(0, np.uint32), np.empty(0, np.uint32), np.empty(0, np.float32)
         return tuple(m.to_numpy(0, n).reshape(-1) for m in (o_r, o_c, o_v))  # only the filled prefix crosses PCIe
@@ -188,6 +197,114 @@ class FusedEdges:
         if self._scratch is not None:
             self._scratch.free()
         self._out = self._scratch = None
+
+
+def vec_copy(src, src_off, dst, dst_off, count):
+    """dst[dst_off + i] = src[src_off + i] for i < count: device vectors of one dtype, on the device (skr_vec_copy)."""
+    _lib.check(_lib.lib().skr_vec_copy(src.ctx._h, src._h, int(src_off), dst._h, int(dst_off), int(count)))
+
+
+class CellList:
+    """A (row, column, value) list that stays on the device: three vectors of `capacity` x 1 cells (uint32, uint32,
+    float32 — a prefix is then a row range, as in FusedEdges) of which the first len(self) are filled.  select_cells and
+    append_from add behind them; a block that does not fit makes the list grow to at least twice its capacity, the
+    filled part carried over on the device (skr_vec_copy)."""
+    DTYPES = (np.uint32, np.uint32, np.float32)
+
+    def __init__(self, ctx, capacity=1 << 16):
+        self.ctx, self.capacity, self.n = ctx, max(1, int(capacity)), 0
+        self.bufs = tuple(ctx.empty(self.capacity, 1, t) for t in self.DTYPES)
+
+    def __len__(self):
+        return self.n
+
+    def reserve(self, total):
+        """Room for `total` cells in all: nothing happens when they fit."""
+        if total <= self.capacity:
+            return
+        capacity = max(int(total), 2 * self.capacity)
+        grown = tuple(self.ctx.empty(capacity, 1, t) for t in self.DTYPES)
+        for old, new in zip(self.bufs, grown):
+            if self.n:
+                vec_copy(old, 0, new, 0, self.n)
+            old.free()  # (stream-ordered: the copy above is enqueued before the memory goes back)
+        self.bufs, self.capacity = grown, capacity
+
+    def append_from(self, rows, cols, vals, count, src_off=0):
+        """Append cells src_off ... src_off + count - 1 of three device vectors (skr_edges' or FusedEdges' outputs)."""
+        count = int(count)
+        self.reserve(self.n + count)
+        for src, dst in zip((rows, cols, vals), self.bufs):
+            vec_copy(src, src_off, dst, self.n, count)
+        self.n += count
+
+    def prefix(self):
+        """Views (rows, cols, vals) of the filled part, each len(self) x 1; None for an empty list."""
+        return tuple(m.view(0, self.n) for m in self.bufs) if self.n else None
+
+    def free(self):
+        for m in self.bufs:
+            m.free()
+        self.bufs, self.n, self.capacity = (), 0, 0
+
+
+def select_cells(r, cutoff, into, nrows=None, col_begin=0, col_end=None, row_global0=0, col_global0=0):
+    """Append the cells of the device block r[0:nrows, col_begin:col_end] with !(v < cutoff) to the CellList `into`, as
+    (row_global0 + i, col_global0 + j, v) in np.nonzero order of the mask: NaN and cells equal to the cutoff are kept,
+    zeros and the diagonal are cells like any other (skr_select_cells_ge).  Returns (count, saw_nan).  into=None: only
+    the count and the flag are made."""
+    ctx = r.ctx
+    nrows = r.rows if nrows is None else nrows
+    col_end = r.cols if col_end is None else col_end
+    count, nan = C.c_int64(0), C.c_int(0)
+    head = (ctx._h, r._h, int(nrows), int(col_begin), int(col_end), int(row_global0), int(col_global0), C.c_float(cutoff))
+    while True:
+        outs = (None, None, None) if into is None else tuple(m._h for m in into.bufs)
+        _lib.check(_lib.lib().skr_select_cells_ge(*head, *outs, 0 if into is None else into.n, C.byref(count), C.byref(nan)))
+        if into is None or into.n + count.value <= into.capacity:
+            break
+        into.reserve(into.n + count.value)  # nothing was written: once more with room
+    if into is not None:
+        into.n += count.value
+    return count.value, bool(nan.value)
+
+
+def pearson_cells(a, b, cutoff, stripe_rows=8192, panel_rows=None):
+    """(cells, saw_nan, panelled): the cells of r = a b^T / K with !(r < cutoff) as a CellList (rows index a, columns
+    index b), whether one of them is NaN, and whether b was cut into panels.  a, b: prepared operands (_lib.Operand) of
+    one storage kind, as neighbors._prepare leaves them.  Per stripe of `stripe_rows` rows of a and per panel of
+    `panel_rows` rows of b (None: all of b): skr_pearson_gemm_op into one reusable [stripe_rows, panel_rows] buffer, then
+    select_cells — pearson_topk's loop.  Without panels the list is row-major; with them it is row-major within each
+    (stripe, panel) block, the blocks in loop order.  The caller frees the list."""
+    ctx = a.ctx
+    n, m = a.rows, b.rows
+    cells = CellList(ctx, max(1 << 16, min(int(2e-3 * n * m), 1 << 26)))
+    if n == 0 or m == 0:
+        return cells, False, False
+    stripe_rows = max(1, min(int(stripe_rows), n))
+    panel_rows = m if panel_rows is None else max(1, min(int(panel_rows), m))
+    buf = ctx.empty(stripe_rows, panel_rows)
+    saw_nan = False
+    try:
+        for s0 in range(0, n, stripe_rows):
+            rows = min(stripe_rows, n - s0)
+            a_s = a if rows == n else a.view(s0, rows)
+            for p0 in range(0, m, panel_rows):
+                cols = min(panel_rows, m - p0)
+                b_p = b if cols == m else b.view(p0, cols)
+                _lib.pearson_gemm_op(ctx, a_s, b_p, buf)
+                _, nan = select_cells(buf, cutoff, cells, nrows=rows, col_begin=0, col_end=cols, row_global0=s0, col_global0=p0)
+                saw_nan = saw_nan or nan
+                if b_p is not b:
+                    b_p.free()
+            if a_s is not a:
+                a_s.free()
+    except BaseException:
+        cells.free()
+        raise
+    finally:
+        buf.free()
+    return cells, saw_nan, panel_rows < m
 
 
 def topk_rows(r, k, nrows=None, col_begin=0, col_end=None, row_global0=0, col_global0=0):
@@ -249,7 +366,7 @@ def pearson_topk(a, b=None, k=10, stripe_rows=8192, panel_rows=None):
 FUSE_MAX_DENSITY = 1e-3  # edges per cell above which the fused epilogue costs more than writing the stripe (measured: 100 000 rows, k = 6)
 
 
-def pearson_edges(z, cutoff, stripe_rows=8192, upper_only=True, engine_gemm=None, fuse="auto"):
+def pearson_edges(z, cutoff, stripe_rows=8192, upper_only=True, engine_gemm=None, fuse="auto", into=None):
     """Edge list of the self-comparison of the prepared operand `z` (seekr_amd._lib.Operand):
     r is produced one stripe of `stripe_rows` rows at a time into one reusable buffer (columns at or
     right of the stripe when `upper_only`) and reduced to edges before the next stripe overwrites
@@ -260,7 +377,10 @@ def pearson_edges(z, cutoff, stripe_rows=8192, upper_only=True, engine_gemm=None
     written; False — the two-step path (contraction into a stripe buffer, then skr_edges); "auto" (default) — fused as
     long as the stripes seen so far hold fewer than FUSE_MAX_DENSITY edges per cell (a sparse list: 15 % faster at
     1e-5 edges per cell; a dense one — the reference's default cutoff 0 keeps half the cells — is cheaper through the
-    stripe buffer).  The result is the same, bit for bit, whichever path a stripe takes."""
+    stripe buffer).  The result is the same, bit for bit, whichever path a stripe takes.
+    into: a CellList every stripe's edges are appended to on the device (the fused buffers' filled prefix, or skr_edges'
+    outputs, through skr_vec_copy) — the same list in the same order, never on the host; the return value is then the
+    number of edges."""
     ctx = z.ctx
     n = z.rows
     stripe_rows = max(1, min(int(stripe_rows), n))
@@ -279,7 +399,7 @@ def pearson_edges(z, cutoff, stripe_rows=8192, upper_only=True, engine_gemm=None
             if z.cols > 1024 and buf is None:
                 buf = ctx.empty(stripe_rows, n)  # k = 7: the earlier k chunks need a block to leave their sums in
             part = fused.block(a, b, cutoff, row_global0=s0, col_global0=c0, upper_only=upper_only, scratch=buf,
-                               retry=fuse is True)
+                               retry=fuse is True, into=into)
             if part is None:  # denser than the list buffers: through the stripe buffer from here on
                 fused.free()
                 fused = None
@@ -288,15 +408,18 @@ def pearson_edges(z, cutoff, stripe_rows=8192, upper_only=True, engine_gemm=None
                 buf = ctx.empty(stripe_rows, n)
             _lib.pearson_gemm_op(ctx, a, b, buf, symmetric=False, row0=0, col0=c0)
             part = edges(buf, cutoff, nrows=rows, col_begin=c0, col_end=n, row_global0=s0, col_global0=0,
-                         upper_only=upper_only)
+                         upper_only=upper_only, into=into)
         seen_cells += rows * (n - c0)
-        seen_edges += len(part[2])
-        for acc, p in zip(out, part):
-            acc.append(p)
+        seen_edges += part if into is not None else len(part[2])
+        if into is None:
+            for acc, p in zip(out, part):
+                acc.append(p)
     if fused:
         fused.free()
     if buf is not None:
         buf.free()
+    if into is not None:
+        return seen_edges
     return tuple(np.concatenate(p) if p else np.empty(0) for p in out)
 
 

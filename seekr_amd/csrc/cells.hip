@@ -1,0 +1,197 @@
+// skr_select_cells_ge: the cells of a query x target block of r with !(v < cutoff) as a (row, column, value) list that
+// stays on the device, and skr_vec_copy, which such a list grows by.  skr_edges (consumers.hip) is the graph's rule — it
+// drops v == 0 and the global diagonal and gives a workgroup to each row; here every cell is an ordinary test and the
+// work is tiled in both directions.
+//
+// A tile is one row x one segment of kCellSegment columns.  Segments are laid out in the row's MEMORY, not in its
+// columns: the first one starts at the 16-byte boundary at or below the row's first selected cell, so that every group
+// of four cells a lane reads is 16-byte aligned whatever the row start, col_begin and the leading dimension are.  A group
+// that lies inside [col_begin, col_end) is one 16-byte load; a group that straddles either end (the head of a row's first
+// segment, the tail of its last) is read cell by cell, the cells outside the range not at all.  Rows whose first cell is
+// not aligned have up to 3 cells fewer in their first segment, which is why a row has ceil((width + 3) / kCellSegment)
+// tiles, the last of which may be empty.
+//
+// Pass 1 counts per tile, radix.hpp's exclusive scan turns the counts into offsets, pass 2 writes.  A cell's place in
+// its tile comes from four wave ballots (one per cell of the lane's group) and the four wave totals: lanes in order,
+// cells in order within the lane — row-major, no atomic per cell, and the same bytes on every run.
+#include <algorithm>
+
+#include "common.hpp"
+#include "radix.hpp"
+
+namespace {
+
+constexpr int kCellBlock = 256, kCellPer = 4, kCellSegment = kCellBlock * kCellPer;  // 1 024: _lib.SELECT_CELLS_SEGMENT
+
+struct CellArgs {
+    const float* r;
+    int64_t ld, rows, col_begin, col_end, row_global0, col_global0, nseg, tiles;
+    float cutoff;
+};
+
+// the lane's four cells of tile t: v[j] and live[j] (inside the column range); c0 = column of v[0]
+__device__ __forceinline__ void load_group(const CellArgs& a, int64_t t, float (&v)[kCellPer], bool (&live)[kCellPer], int64_t& row,
+                                           int64_t& c0) {
+    row = t / a.nseg;
+    const int64_t seg = t - row * a.nseg;
+    const float* rowp = a.r + (size_t)row * (size_t)a.ld;
+    const int64_t mis = (int64_t)(((uintptr_t)(rowp + a.col_begin) >> 2) & 3);  // cells from the 16-byte boundary below to the first selected cell
+    c0 = a.col_begin - mis + seg * kCellSegment + (int64_t)threadIdx.x * kCellPer;
+    if (c0 >= a.col_begin && c0 + kCellPer <= a.col_end) {
+        const float4 q = *reinterpret_cast<const float4*>(rowp + c0);  // 16-byte aligned by construction
+        v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+#pragma unroll
+        for (int j = 0; j < kCellPer; j++) live[j] = true;
+    } else {
+#pragma unroll
+        for (int j = 0; j < kCellPer; j++) {
+            live[j] = c0 + j >= a.col_begin && c0 + j < a.col_end;
+            v[j] = live[j] ? rowp[c0 + j] : 0.f;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kCellBlock) void cells_count_pass(CellArgs a, unsigned long long* __restrict__ counts,
+                                                                 unsigned* __restrict__ nan_flag) {
+    __shared__ unsigned red[2][kCellBlock / 64];  // two sets: one barrier per tile
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    bool nan = false;
+    int set = 0;
+    for (int64_t t = blockIdx.x; t < a.tiles; t += gridDim.x, set ^= 1) {
+        float v[kCellPer];
+        bool live[kCellPer];
+        int64_t row, c0;
+        load_group(a, t, v, live, row, c0);
+        unsigned n = 0;
+#pragma unroll
+        for (int j = 0; j < kCellPer; j++) {
+            const bool keep = live[j] && !(v[j] < a.cutoff);
+            nan = nan || (keep && v[j] != v[j]);
+            n += (unsigned)__popcll(__ballot(keep));
+        }
+        if (lane == 0) red[set][wave] = n;
+        __syncthreads();
+        if (threadIdx.x == 0) counts[t] = (unsigned long long)red[set][0] + red[set][1] + red[set][2] + red[set][3];
+    }
+    if (nan) atomicOr(nan_flag, 1u);
+}
+
+__global__ __launch_bounds__(kCellBlock) void cells_fill_pass(CellArgs a, const unsigned long long* __restrict__ offsets,
+                                                                unsigned long long out_offset, uint32_t* __restrict__ out_row,
+                                                                uint32_t* __restrict__ out_col, float* __restrict__ out_val) {
+    __shared__ unsigned wave_n[2][kCellBlock / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
+    int set = 0;
+    for (int64_t t = blockIdx.x; t < a.tiles; t += gridDim.x) {
+        const unsigned long long base = offsets[t];
+        if (offsets[t + 1] == base) continue;  // nothing kept in this tile (the same for every lane of the workgroup)
+        float v[kCellPer];
+        bool live[kCellPer], keep[kCellPer];
+        int64_t row, c0;
+        load_group(a, t, v, live, row, c0);
+        unsigned lower = 0, all = 0;  // kept cells of the lower lanes of this wave; of the whole wave
+#pragma unroll
+        for (int j = 0; j < kCellPer; j++) {
+            keep[j] = live[j] && !(v[j] < a.cutoff);
+            const unsigned long long mask = __ballot(keep[j]);
+            lower += (unsigned)__popcll(mask & below);
+            all += (unsigned)__popcll(mask);
+        }
+        if (lane == 0) wave_n[set][wave] = all;
+        __syncthreads();
+        unsigned before = 0;
+#pragma unroll
+        for (int w = 0; w < kCellBlock / 64; w++)
+            if (w < wave) before += wave_n[set][w];
+        unsigned long long pos = out_offset + base + before + lower;
+#pragma unroll
+        for (int j = 0; j < kCellPer; j++)
+            if (keep[j]) {
+                out_row[pos] = (uint32_t)(a.row_global0 + row);
+                out_col[pos] = (uint32_t)(a.col_global0 + c0 + j);
+                out_val[pos] = v[j];
+                pos++;
+            }
+        set ^= 1;
+    }
+}
+
+}  // namespace
+
+extern "C" int skr_select_cells_ge(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t col_begin, int64_t col_end,
+                                   int64_t row_global0, int64_t col_global0, float cutoff, skr_mat* out_rows,
+                                   skr_mat* out_cols, skr_mat* out_vals, int64_t out_offset, int64_t* count, int* saw_nan) {
+    SKR_REQUIRE(ctx && r && count && r->ctx == ctx && r->dtype == SKR_F32, "need a float32 matrix of this ctx and a count");
+    SKR_REQUIRE(nrows >= 0 && nrows <= r->rows, "nrows out of range");
+    SKR_REQUIRE(col_begin >= 0 && col_begin <= col_end && col_end <= r->cols, "column range out of the matrix");
+    SKR_REQUIRE(row_global0 >= 0 && col_global0 >= 0 && row_global0 + nrows <= 0xffffffffLL &&
+                    col_global0 + col_end <= 0xffffffffLL, "global indices must fit 32 bits");
+    const bool fill = out_rows || out_cols || out_vals;
+    int64_t cap = 0;
+    if (fill) {
+        SKR_REQUIRE(out_rows && out_cols && out_vals, "pass all three outputs or none");
+        SKR_REQUIRE(out_rows->ctx == ctx && out_cols->ctx == ctx && out_vals->ctx == ctx, "foreign ctx");
+        SKR_REQUIRE(out_rows->dtype == SKR_U32 && out_cols->dtype == SKR_U32 && out_vals->dtype == SKR_F32,
+                    "outputs are U32, U32, F32");
+        SKR_REQUIRE(out_offset >= 0, "out_offset must not be negative");
+        cap = std::min(out_rows->rows * out_rows->cols, std::min(out_cols->rows * out_cols->cols, out_vals->rows * out_vals->cols));
+    }
+    SKR_TRY(skr_activate(ctx));
+    *count = 0;
+    if (saw_nan) *saw_nan = 0;
+    if (nrows == 0 || col_begin == col_end) return SKR_OK;
+    CellArgs a{(const float*)r->data, r->cols, nrows, col_begin, col_end, row_global0, col_global0, 0, 0, cutoff};
+    a.nseg = (col_end - col_begin + (kCellPer - 1) + kCellSegment - 1) / kCellSegment;
+    a.tiles = nrows * a.nseg;
+    void* ws = nullptr;
+    // per-tile counts and a zero behind them: scanned in place, offsets[tiles] is the total.  Then the scan's scratch and
+    // the NaN flag.
+    const size_t scan_words = skr_radix::scan_scratch_words(a.tiles + 1);
+    SKR_TRY(skr_ctx_workspace(ctx, ((size_t)a.tiles + 1 + scan_words + 1) * 8, &ws));
+    unsigned long long* counts = (unsigned long long*)ws;
+    unsigned long long* total = counts + a.tiles;
+    unsigned* nan_flag = (unsigned*)(total + 1 + scan_words);
+    SKR_HIP(hipMemsetAsync(total, 0, 8, ctx->stream));
+    SKR_HIP(hipMemsetAsync(nan_flag, 0, 8, ctx->stream));
+    const unsigned grid = (unsigned)std::min<int64_t>(a.tiles, (int64_t)ctx->num_cu * 16);
+    {
+        SkrProfScope prof(ctx, "cells_count");
+        hipLaunchKernelGGL(cells_count_pass, dim3(grid), dim3(kCellBlock), 0, ctx->stream, a, counts, nan_flag);
+        SKR_HIP(hipGetLastError());
+    }
+    SKR_TRY(skr_radix::exclusive_scan<unsigned long long>(ctx, counts, a.tiles + 1, total + 1));
+    unsigned long long h_total = 0;
+    unsigned h_nan = 0;
+    SKR_HIP(hipMemcpyAsync(&h_total, total, 8, hipMemcpyDeviceToHost, ctx->stream));
+    SKR_HIP(hipMemcpyAsync(&h_nan, nan_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
+    SKR_HIP(hipStreamSynchronize(ctx->stream));
+    *count = (int64_t)h_total;
+    if (saw_nan) *saw_nan = h_nan ? 1 : 0;
+    if (!fill || h_total == 0) return SKR_OK;
+    if (out_offset > cap || (int64_t)h_total > cap - out_offset) return SKR_OK;  // does not fit: the caller grows its buffers
+    SkrProfScope prof(ctx, "cells_fill");
+    hipLaunchKernelGGL(cells_fill_pass, dim3(grid), dim3(kCellBlock), 0, ctx->stream, a, counts, (unsigned long long)out_offset,
+                       (uint32_t*)out_rows->data, (uint32_t*)out_cols->data, (float*)out_vals->data);
+    SKR_HIP(hipGetLastError());
+    return SKR_OK;
+}
+
+extern "C" int skr_vec_copy(skr_ctx* ctx, const skr_mat* src, int64_t src_off, skr_mat* dst, int64_t dst_off, int64_t count) {
+    SKR_REQUIRE(ctx && src && dst, "NULL argument");
+    SKR_REQUIRE(src->ctx == ctx && dst->ctx == ctx, "foreign ctx");
+    SKR_REQUIRE(src->dtype == dst->dtype, "src and dst must have the same dtype");
+    SKR_REQUIRE(src->dtype == SKR_U32 || src->dtype == SKR_F32 || src->dtype == SKR_F64, "U32, F32 or F64 cells");
+    SKR_REQUIRE(count >= 0 && src_off >= 0 && dst_off >= 0, "offsets and count must not be negative");
+    SKR_REQUIRE(src_off <= src->rows * src->cols && count <= src->rows * src->cols - src_off, "range outside src");
+    SKR_REQUIRE(dst_off <= dst->rows * dst->cols && count <= dst->rows * dst->cols - dst_off, "range outside dst");
+    SKR_TRY(skr_activate(ctx));
+    if (count == 0) return SKR_OK;
+    const size_t elem = src->elem();
+    const char* s = (const char*)src->data + (size_t)src_off * elem;
+    char* d = (char*)dst->data + (size_t)dst_off * elem;
+    const size_t bytes = (size_t)count * elem;
+    SKR_REQUIRE(s + bytes <= d || d + bytes <= s, "the ranges overlap");
+    SKR_HIP(hipMemcpyAsync(d, s, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    return SKR_OK;
+}

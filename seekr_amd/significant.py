@@ -1,6 +1,7 @@
-"""The significantly similar pairs of a self-comparison on MI355X without any N x N matrix: which cells of the corrected
-p-value matrix are <= alpha, with their r, p and corrected p.  The reference answers this with three matrices (pearson,
-find_pval, adj_pval); the specification here is this package's own full-matrix path on the same operand,
+"""The significantly similar pairs of a self-comparison, or of one set of rows against another, on MI355X without any
+N x N matrix: which cells of the corrected p-value matrix are <= alpha, with their r, p and corrected p.  The reference
+answers this with three matrices (pearson, find_pval, adj_pval); the specification here is this package's own
+full-matrix path on the same operand,
 
     r = pearson_gemm_op(z, z);  p = parametric_pvalues(r, ...) or empirical_pvalues(r, ...)
     p_adj = adjust_pvalues(p, method, alpha, symmetric=True);  the cells p_adj <= alpha in np.nonzero order
@@ -9,6 +10,12 @@ bit for bit.  It rests on two facts (DESIGN_PARITY.md, "significant_pairs"): a p
 r, so the cells with p <= alpha are the cells with r >= r0 for a cutoff found before the contraction runs, which the
 fused edge list delivers; and for the seven methods of consumers.HEAD_METHODS a corrected value <= alpha depends only on
 the tests with p <= alpha and on the number of tests (consumers.adjust_pvalues_head).
+
+Two sets (`other`, `counts2`): the reference's find_pval(seq1file, seq2file) followed by adj_pval on the whole
+non-symmetric matrix.  The specification is the same path with symmetric=False and n1 x n2 tests; every cell is a test, the
+cell (i, i) included, so the candidates come from consumers.pearson_cells (skr_select_cells_ge: no zero rule, no diagonal
+rule) and never leave the device.  p_adj is float64 here whatever the method: for bonferroni and sidak, which the full
+path returns in float32, it is the widening of that float32 (DESIGN_PARITY.md).
 """
 import numpy as np
 
@@ -19,9 +26,10 @@ SEARCH_LO, SEARCH_HI = np.float32(-2.0), np.float32(2.0)
 
 
 class SignificantPairs:
-    """rows, cols (uint32, row < col), r, p (float32), p_adj (float64): the significant pairs in np.nonzero order;
-    n_tests = N (N - 1) / 2, r_cutoff = the cutoff the edge list was taken at (None when the search found none),
-    n_candidates = the length of that list."""
+    """rows, cols (uint32), r, p (float32), p_adj (float64): the significant pairs in np.nonzero order;
+    r_cutoff = the cutoff the candidate list was taken at (None when the search found none), n_candidates = the length
+    of that list.  Self-comparison: row < col, both index the one set, n_tests = N (N - 1) / 2.  Two sets: rows index
+    the first set (`z`, `counts`), cols the second (`other`, `counts2`), n_tests = N1 N2."""
 
     def __init__(self, n_tests, r_cutoff=None, n_candidates=0, rows=None, cols=None, r=None, p=None, p_adj=None):
         self.n_tests, self.r_cutoff, self.n_candidates = int(n_tests), r_cutoff, int(n_candidates)
@@ -136,16 +144,56 @@ class _PValues:
             self.bg = None
 
 
-def _check_arguments(fitres, bestfit, method, alpha):
+def row_major_order(rows, cols):
+    """The permutation that puts a (row, col) list into np.nonzero order: by row, then by column."""
+    return np.lexsort((np.asarray(cols), np.asarray(rows)))
+
+
+NAN_MESSAGE = ("r is NaN for some pair (a constant row): every corrected p-value of the full-matrix path is NaN as well; "
+               "remove such rows first")
+
+
+def _check_arguments(fitres, bestfit, method, alpha, candidates="host"):
     name = consumers.head_method(method)
     if not 0 < float(alpha) < 1:
         raise ValueError("alpha must lie strictly between 0 and 1 (got {!r})".format(alpha))
+    if candidates not in ("host", "device"):
+        raise ValueError("candidates must be 'host' or 'device' (got {!r})".format(candidates))
     if not isinstance(fitres, np.ndarray):
         fitres[bestfit - 1]  # the IndexError find_pval gives (find_pval.py:118)
     return name
 
 
-def pearson_significant(z, fitres, bestfit=1, method="fdr_bh", alpha=0.05, stripe_rows=8192, fuse="auto", timings=None):
+def correct_candidates(pv, d_rows, d_cols, d_r, n_tests, name, alpha, held, lap=lambda step: None):
+    """From the candidate list on the device (three vectors: row, column, r; every cell with p <= alpha among them) to
+    the significant cells on the host: [rows, cols, r, p, p_adj] in the list's order, or None when there are none.  The
+    p-values of the candidates (pv: _PValues), the cells with p <= alpha, their correction among all n_tests tests
+    (consumers.adjust_pvalues_head, method `name`), the cells with corrected p <= alpha; only those leave the device.
+    Every device matrix made on the way is appended to `held` for the caller to free."""
+    d_p = pv(d_r)
+    held.append(d_p)
+    lap("p_values")
+    idx, kept = consumers.select_le(d_p, float(alpha_float32(alpha)))
+    if kept == 0:
+        return None
+    held.append(idx)
+    lists = [consumers.gather_index(m, idx, kept) for m in (d_rows, d_cols, d_r, d_p)]
+    held += lists
+    lap("selection")
+    d_adj = consumers.adjust_pvalues_head(lists[3], n_tests, name, alpha)
+    held.append(d_adj)
+    lap("correction")
+    idx2, sig = consumers.select_le(d_adj, float(alpha))
+    if sig == 0:
+        return None
+    held.append(idx2)
+    final = [consumers.gather_index(m, idx2, sig) for m in lists + [d_adj]]
+    held += final
+    return [np.array(m.to_numpy()).reshape(-1) for m in final]
+
+
+def pearson_significant(z, fitres, bestfit=1, method="fdr_bh", alpha=0.05, stripe_rows=8192, fuse="auto", timings=None,
+                        other=None, panel_rows=None, candidates="host"):
     """The significant pairs (SignificantPairs) of the self-comparison of the prepared operand `z` (seekr_amd._lib.Operand,
     as pearson_edges takes it): the cells of adjust_pvalues(p, method, alpha, symmetric=True) that are <= alpha, with
     p = find_pval's p-values of r against `fitres` — find_dist's list of (name, deviance, parameters) (entry `bestfit`,
@@ -155,12 +203,20 @@ def pearson_significant(z, fitres, bestfit=1, method="fdr_bh", alpha=0.05, strip
     candidate list pearson_edges(z, r0) (stripe_rows, fuse: as there), its p-values, the cells with p <= alpha,
     their correction among all N (N - 1) / 2 tests, the cells with corrected p <= alpha.  The candidate list is uploaded
     once; after that only the final lists leave the device.  ValueError: r0 <= 0 (use the full-matrix path), a NaN
-    among the candidates (a constant row).  `timings`: a dict that receives the seconds of each step."""
+    among the candidates (a constant row).  `timings`: a dict that receives the seconds of each step.
+
+    candidates="device": the candidate list never visits the host — the fused buffers' filled prefix (or skr_edges'
+    outputs) is appended to a consumers.CellList with skr_vec_copy; the result is the same in every byte.
+
+    other: a second prepared operand of z's storage kind (neighbors._prepare): the rows of z against the rows of `other`,
+    n_tests = z.rows x other.rows, every cell a test.  The candidates are consumers.pearson_cells(z, other, r0,
+    stripe_rows, panel_rows) and stay on the device (`fuse` and `candidates` do not apply); with panels the final lists
+    are put into (row, col) order on the host.  rows index z, cols index `other`."""
     import time
-    name = _check_arguments(fitres, bestfit, method, alpha)
+    name = _check_arguments(fitres, bestfit, method, alpha, candidates)
     ctx = z.ctx
     n = z.rows
-    n_tests = n * (n - 1) // 2
+    n_tests = n * (n - 1) // 2 if other is None else n * other.rows
     if n_tests == 0:
         return SignificantPairs(n_tests)
     alpha32 = alpha_float32(alpha)
@@ -181,39 +237,52 @@ def pearson_significant(z, fitres, bestfit=1, method="fdr_bh", alpha=0.05, strip
         if r_star is None:
             return SignificantPairs(n_tests)
         r0 = cutoff_with_guard(r_star)
-        rows, cols, vals = consumers.pearson_edges(z, float(r0), stripe_rows=stripe_rows, upper_only=True, fuse=fuse)
-        n_cand = len(vals)
-        lap("edge_list")
-        if n_cand == 0:
-            return SignificantPairs(n_tests, r0, 0)
-        if np.isnan(vals).any():
-            raise ValueError("r is NaN for some pair (a constant row): every corrected p-value of the full-matrix path is "
-                             "NaN as well; remove such rows first")
-        d_rows, d_cols, d_r = (ctx.from_numpy(np.ascontiguousarray(a)) for a in (rows.astype(np.uint32, copy=False),
-                                                                                cols.astype(np.uint32, copy=False), vals))
-        held += [d_rows, d_cols, d_r]
-        if timings is not None:
-            timings["bytes_to_device"] = n_cand * 12
-        d_p = pv(d_r)
-        held.append(d_p)
-        lap("p_values")
-        idx, kept = consumers.select_le(d_p, float(alpha32))
-        if kept == 0:
+        panelled = False
+        if other is not None or candidates == "device":
+            if other is not None:
+                cells, saw_nan, panelled = consumers.pearson_cells(z, other, float(r0), stripe_rows=stripe_rows,
+                                                                   panel_rows=panel_rows)
+                held.append(cells)
+            else:
+                cells = consumers.CellList(ctx)
+                held.append(cells)
+                consumers.pearson_edges(z, float(r0), stripe_rows=stripe_rows, upper_only=True, fuse=fuse, into=cells)
+                saw_nan = False
+                if len(cells):  # a NaN among the values: the cells of the value vector (one column) that are not below +inf
+                    views = cells.prefix()
+                    saw_nan = consumers.select_cells(views[2], np.inf, None)[1]
+                    for v in views:
+                        v.free()
+            n_cand = len(cells)
+            lap("edge_list")
+            if n_cand == 0:
+                return SignificantPairs(n_tests, r0, 0)
+            if saw_nan:
+                raise ValueError(NAN_MESSAGE)
+            d_rows, d_cols, d_r = cells.prefix()
+            held[:0] = [d_rows, d_cols, d_r]  # the views go before the list they look into
+            if timings is not None:
+                timings["bytes_to_device"] = 0
+        else:
+            rows, cols, vals = consumers.pearson_edges(z, float(r0), stripe_rows=stripe_rows, upper_only=True, fuse=fuse)
+            n_cand = len(vals)
+            lap("edge_list")
+            if n_cand == 0:
+                return SignificantPairs(n_tests, r0, 0)
+            if np.isnan(vals).any():
+                raise ValueError(NAN_MESSAGE)
+            d_rows, d_cols, d_r = (ctx.from_numpy(np.ascontiguousarray(a)) for a in (rows.astype(np.uint32, copy=False),
+                                                                                    cols.astype(np.uint32, copy=False), vals))
+            held += [d_rows, d_cols, d_r]
+            if timings is not None:
+                timings["bytes_to_device"] = n_cand * 12
+        out = correct_candidates(pv, d_rows, d_cols, d_r, n_tests, name, alpha, held, lap)
+        if out is None:
             return SignificantPairs(n_tests, r0, n_cand)
-        held.append(idx)
-        lists = [consumers.gather_index(m, idx, kept) for m in (d_rows, d_cols, d_r, d_p)]
-        held += lists
-        lap("selection")
-        d_adj = consumers.adjust_pvalues_head(lists[3], n_tests, name, alpha)
-        held.append(d_adj)
-        lap("correction")
-        idx2, sig = consumers.select_le(d_adj, float(alpha))
-        if sig == 0:
-            return SignificantPairs(n_tests, r0, n_cand)
-        held.append(idx2)
-        final = [consumers.gather_index(m, idx2, sig) for m in lists + [d_adj]]
-        held += final
-        out = [np.array(m.to_numpy()).reshape(-1) for m in final]
+        sig = len(out[0])
+        if panelled:  # the list came block by block: np.nonzero order is restored on the few cells that are left
+            order = row_major_order(out[0], out[1])
+            out = [a[order] for a in out]
         lap("selection")
         if timings is not None:
             timings["bytes_to_host"] = sig * (4 + 4 + 4 + 4 + 8)
@@ -225,17 +294,27 @@ def pearson_significant(z, fitres, bestfit=1, method="fdr_bh", alpha=0.05, strip
 
 
 @_lib.api_call
-def significant_pairs(counts, fitres, bestfit=1, method="fdr_bh", alpha=0.05, **kw):
+def significant_pairs(counts, fitres, bestfit=1, method="fdr_bh", alpha=0.05, counts2=None, **kw):
     """pearson_significant for a host count matrix (anything np.ascontiguousarray(.., float32) accepts): the rows are
-    prepared as pearson() and nearest() prepare a self-comparison.  `kw`: stripe_rows, fuse, timings."""
+    prepared as pearson() and nearest() prepare a self-comparison.  counts2 (not None and not `counts` itself): the
+    rows of counts against the rows of counts2, both prepared as pearson() and nearest() prepare two sets.
+    `kw`: stripe_rows, fuse, timings, panel_rows, candidates."""
     from seekr_amd import neighbors
-    _check_arguments(fitres, bestfit, method, alpha)
+    _check_arguments(fitres, bestfit, method, alpha, kw.get("candidates", "host"))
+    same = counts2 is None or counts2 is counts
     c = neighbors._f32(counts)
-    if c.ndim != 2:
+    c2 = c if same else neighbors._f32(counts2)
+    if c.ndim != 2 or c2.ndim != 2:
         raise ValueError("counts must be a 2-D matrix")
+    if c.shape[1] != c2.shape[1]:
+        raise ValueError("counts and counts2 must have the same number of columns ({} and {})".format(c.shape[1], c2.shape[1]))
+    if not same and (c.shape[0] == 0 or c2.shape[0] == 0):
+        return SignificantPairs(0)
     ctx = _lib.default_context()
-    z, _ = neighbors._prepare(ctx, c, c, True)
+    z, z2 = neighbors._prepare(ctx, c, c2, same)
     try:
-        return pearson_significant(z, fitres, bestfit=bestfit, method=method, alpha=alpha, **kw)
+        return pearson_significant(z, fitres, bestfit=bestfit, method=method, alpha=alpha, other=z2, **kw)
     finally:
         z.free()
+        if z2 is not None:
+            z2.free()

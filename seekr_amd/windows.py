@@ -287,6 +287,81 @@ def domain_topk(query, target, k, window, slide, mean, std, top=10, log2="Log2.p
                    "start": run.start[win], "end": run.start[win] + run.length[win], "r": rv})
 
 
+@_lib.api_call
+def domain_significant(query, target, k, window, slide, mean, std, fitres, bestfit=1, method="fdr_bh", alpha=0.05,
+                       log2="Log2.post", chunk_rows=65536):
+    """The windows of the target each query is significantly similar to: a DataFrame with one row per significant (query,
+    window) cell in that order and the columns `query` (its index), `header`, `start`, `end` (the window), `r`, `p` and
+    `p_adj` — the cells with p_adj <= alpha of domain_pearson's r for the same arguments taken through the full-matrix
+    path (p-values against `fitres`, entry `bestfit`, as seekr_amd.significant takes them; consumers.adjust_pvalues on
+    all n_query x n_windows tests, `method` one of consumers.HEAD_METHODS).  frame.attrs: n_tests, r_cutoff (None when
+    the background never reaches alpha), n_candidates.
+
+    domain_pearson's loop with one change: the cells of each chunk's block with r at or above the cutoff
+    (significant.find_cutoff, lowered by its guard) are appended to a list on the device (skr_select_cells_ge) and r is
+    never downloaded; the list is corrected as significant.pearson_significant corrects its candidates and only the
+    significant cells cross PCIe.  ValueError: the cutoff is not positive, or r is NaN for a candidate (the first such
+    window is named; usually a window of fewer than k letters).  NAN_WARNING as in domain_topk."""
+    from seekr_amd import consumers
+    from seekr_amd import significant as sg
+    name = sg._check_arguments(fitres, bestfit, method, alpha)
+    run = _DomainRun(query, target, k, window, slide, mean, std, log2, chunk_rows, "domain_significant")
+    ctx, n_tests = run.ctx, run.n_query * run.n_rows
+    attrs = {"n_tests": n_tests, "r_cutoff": None, "n_candidates": 0}
+
+    def frame(q, win, r, p, p_adj):
+        headers = run.headers()
+        out = _frame({"query": q, "header": headers[run.seq_index[win]] if len(win) else headers[:0], "start": run.start[win],
+                      "end": run.start[win] + run.length[win], "r": r, "p": p, "p_adj": p_adj})
+        out.attrs.update(attrs)
+        return out
+
+    none = np.empty(0, np.int64)
+    empty = (none, none, np.empty(0, np.float32), np.empty(0, np.float32), np.empty(0, np.float64))
+    if n_tests == 0:
+        return frame(*empty)
+    pv = sg._PValues(ctx, fitres, bestfit)
+    held = []
+    try:
+        r_star = sg.find_cutoff(pv.host, sg.alpha_float32(alpha))
+        if r_star is None:
+            return frame(*empty)
+        cutoff = sg.cutoff_with_guard(r_star)
+        attrs["r_cutoff"] = cutoff
+        cells = consumers.CellList(ctx)
+        held.append(cells)
+        nan_seen, nan_window = False, None
+        for r0, n, r_dev, has_nan in run.blocks():
+            _, saw = consumers.select_cells(r_dev, float(cutoff), cells, nrows=run.n_query, col_begin=0, col_end=n,
+                                            row_global0=0, col_global0=r0)
+            nan_seen = nan_seen or has_nan or saw
+            if saw:  # (rare: the block is fetched to name the window)
+                nan_window = r0 + int(np.isnan(r_dev.to_numpy()[:, :n]).any(axis=0).argmax())
+                break
+        if nan_seen:
+            print(NAN_WARNING)
+        if nan_window is not None:
+            w = nan_window
+            raise ValueError("r is NaN for window {} ({}:{}-{}; a window of fewer than k letters has no r): every corrected "
+                             "p-value of the full-matrix path is NaN as well; leave such windows out".format(
+                                 w, run.headers()[run.seq_index[w]], run.start[w], run.start[w] + run.length[w]))
+        attrs["n_candidates"] = len(cells)
+        if len(cells) == 0:
+            return frame(*empty)
+        views = list(cells.prefix())
+        held[:0] = views
+        out = sg.correct_candidates(pv, *views, n_tests, name, alpha, held)
+        if out is None:
+            return frame(*empty)
+        order = sg.row_major_order(out[0], out[1])  # the list came chunk by chunk
+        q, win, r, p, p_adj = (a[order] for a in out)
+        return frame(q.astype(np.int64), win.astype(np.int64), r, p, p_adj)
+    finally:
+        pv.free()
+        for m in held:
+            m.free()
+
+
 def window_labels(table):
     """`header:start-end` of every row of domain_pearson's table: the column labels of r in a labelled CSV."""
     return ["{}:{}-{}".format(h, s, e) for h, s, e in zip(table["header"], table["start"], table["end"])]

@@ -22,6 +22,8 @@ setup(
             "seekr_nearest = seekr_amd.console_scripts:console_nearest",
             # the pairs with a corrected p-value <= alpha, without r, p or the corrected matrix (no counterpart either)
             "seekr_significant_pairs = seekr_amd.console_scripts:console_significant_pairs",
+            # the windows of a target each query is significantly similar to (no counterpart either)
+            "seekr_domain_significant = seekr_amd.console_scripts:console_domain_significant",
             "seekr_kmer_leiden = seekr_amd.console_scripts:console_kmer_leiden",
         ]
     },
