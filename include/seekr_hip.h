@@ -551,6 +551,23 @@ int skr_leiden(skr_ctx* ctx, const skr_mat* rows, const skr_mat* cols, const skr
                int64_t* levels_run);
 int skr_leiden_last(int* converged, int64_t* sweeps);
 int skr_leiden_limits(int* wave_degree, int* lds_degree);
+/* The most workgroups, each with a table of its own, that the device-memory work unit runs at once on ctx's device (twice
+ * its CU count): a level with more nodes above lds_degree gives every workgroup several, one after the other.           */
+int skr_leiden_table_groups(skr_ctx* ctx, int* groups);
+/* A trace of the calling thread's skr_leiden runs, for tests (host code only: with it off, the default, skr_leiden does
+ * nothing more than before).  skr_leiden_trace(on, dump_record) clears the record and switches it.  While on, every run
+ * appends records of 8 uint64 words; word 0 is the kind, `level` counts from 0 (the input graph), the hashes are
+ * FNV-1a 64 of the array's bytes, and unused words are 0:
+ *   1  after a proposal pass of local moving:  level, nodes, nodes of the workgroup unit, nodes of the device-memory
+ *      unit, hash of prop (uint32 [nodes], 0xFFFFFFFF = stays), hash of the gains (float64 [nodes])
+ *   2  after a refinement round:  level, nodes, the two unit counts, hash of prop, hash of target (uint32 [nodes]),
+ *      nodes moved
+ *   3  after a sweep was measured:  level, tries, moves, the bits of its quality, labels in use, 1 if it was kept
+ * skr_leiden_trace_read gives *words and, where capacity >= *words, the words.  dump_record >= 0 also keeps the two
+ * arrays of that record (kinds 1 and 2) whole for skr_leiden_trace_dump, which works the same way with bytes.        */
+int skr_leiden_trace(int on, int64_t dump_record);
+int skr_leiden_trace_read(uint64_t* out, int64_t capacity, int64_t* words);
+int skr_leiden_trace_dump(void* a, int64_t capacity_a, void* b, int64_t capacity_b, int64_t* bytes_a, int64_t* bytes_b);
 
 /* ---------------------------------------------------------------- one-call host forms --- */
 /* The two reference calls of the hot path over caller-owned host buffers, for bindings that do

@@ -135,6 +135,10 @@ SIGNATURES = {
                           C.POINTER(_i64)]),
     "skr_leiden_last": (_int, [C.POINTER(_int), C.POINTER(_i64)]),
     "skr_leiden_limits": (_int, [C.POINTER(_int), C.POINTER(_int)]),
+    "skr_leiden_table_groups": (_int, [_p, C.POINTER(_int)]),
+    "skr_leiden_trace": (_int, [_int, _i64]),
+    "skr_leiden_trace_read": (_int, [_p, _i64, C.POINTER(_i64)]),
+    "skr_leiden_trace_dump": (_int, [_p, _i64, _p, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
     "skr_mat_save_npy": (_int, [_p, _p, _int, C.c_char_p]),
     "skr_mat_save_csv": (_int, [_p, _p, _int, _int, C.c_char_p]),
     "skr_host_save_npy": (_int, [_p, _int, _i64, _i64, _int, C.c_char_p]),

@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <vector>
 
 #include "common.hpp"
 #include "radix.hpp"
@@ -632,7 +633,72 @@ struct Sorter {
 thread_local int g_converged = 1;
 thread_local int64_t g_sweeps = 0;
 
+// ---- the trace (skr_leiden_trace): host code only.  While it is on, the driver appends one record of kTraceWords
+// uint64 words after every proposal pass of local moving, every refinement round and every measured sweep; the
+// arrays a proposal wrote are copied to the host and hashed there.  Off (the default) nothing below runs.
+constexpr int kTraceWords = 8;
+constexpr u64 kTracePropose = 1, kTraceRefine = 2, kTraceSweep = 3;
+struct Trace {
+    bool on = false;
+    int64_t dump = -1;           // the record whose arrays are kept whole
+    std::vector<uint64_t> words;
+    std::vector<unsigned char> a, b;  // of record `dump`: prop, and pgain (local moving) or target (refinement)
+};
+thread_local Trace g_trace;
+
+uint64_t fnv1a64(const unsigned char* p, size_t bytes) {
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (size_t i = 0; i < bytes; i++) h = (h ^ p[i]) * 0x100000001b3ull;
+    return h;
+}
+
+// one record that hashes two device arrays: copies them on the stream, waits, hashes.  head: the words before the hashes
+int trace_arrays(hipStream_t st, const uint64_t* head, int n_head, const void* d_a, size_t bytes_a, const void* d_b, size_t bytes_b,
+                 uint64_t tail) {
+    Trace& T = g_trace;
+    std::vector<unsigned char> a(bytes_a), b(bytes_b);
+    if (bytes_a) SKR_HIP(hipMemcpyAsync(a.data(), d_a, bytes_a, hipMemcpyDeviceToHost, st));
+    if (bytes_b) SKR_HIP(hipMemcpyAsync(b.data(), d_b, bytes_b, hipMemcpyDeviceToHost, st));
+    SKR_HIP(hipStreamSynchronize(st));
+    uint64_t rec[kTraceWords] = {0};
+    for (int i = 0; i < n_head; i++) rec[i] = head[i];
+    rec[n_head] = fnv1a64(a.data(), bytes_a);
+    rec[n_head + 1] = fnv1a64(b.data(), bytes_b);
+    rec[n_head + 2] = tail;
+    if ((int64_t)(T.words.size() / kTraceWords) == T.dump) {
+        T.a.swap(a);
+        T.b.swap(b);
+    }
+    T.words.insert(T.words.end(), rec, rec + kTraceWords);
+    return SKR_OK;
+}
+
 }  // namespace
+
+extern "C" int skr_leiden_trace(int on, int64_t dump_record) {
+    g_trace.on = on != 0;
+    g_trace.dump = on ? dump_record : -1;
+    g_trace.words.clear();
+    g_trace.a.clear();
+    g_trace.b.clear();
+    return SKR_OK;
+}
+
+extern "C" int skr_leiden_trace_read(uint64_t* out, int64_t capacity, int64_t* words) {
+    SKR_REQUIRE(words && capacity >= 0 && (out || capacity == 0), "NULL argument");
+    *words = (int64_t)g_trace.words.size();
+    if (capacity >= *words && *words) memcpy(out, g_trace.words.data(), (size_t)*words * 8);
+    return SKR_OK;
+}
+
+extern "C" int skr_leiden_trace_dump(void* a, int64_t capacity_a, void* b, int64_t capacity_b, int64_t* bytes_a, int64_t* bytes_b) {
+    SKR_REQUIRE(bytes_a && bytes_b && capacity_a >= 0 && capacity_b >= 0, "NULL argument");
+    *bytes_a = (int64_t)g_trace.a.size();
+    *bytes_b = (int64_t)g_trace.b.size();
+    if (a && capacity_a >= *bytes_a && *bytes_a) memcpy(a, g_trace.a.data(), (size_t)*bytes_a);
+    if (b && capacity_b >= *bytes_b && *bytes_b) memcpy(b, g_trace.b.data(), (size_t)*bytes_b);
+    return SKR_OK;
+}
 
 extern "C" int skr_leiden_last(int* converged, int64_t* sweeps) {
     if (converged) *converged = g_converged;
@@ -643,6 +709,12 @@ extern "C" int skr_leiden_last(int* converged, int64_t* sweeps) {
 extern "C" int skr_leiden_limits(int* wave_degree, int* lds_degree) {
     if (wave_degree) *wave_degree = kWaveDeg;
     if (lds_degree) *lds_degree = kLdsDeg;
+    return SKR_OK;
+}
+
+extern "C" int skr_leiden_table_groups(skr_ctx* ctx, int* groups) {
+    SKR_REQUIRE(ctx && groups, "NULL argument");
+    *groups = ctx->num_cu * 2;
     return SKR_OK;
 }
 
@@ -847,6 +919,10 @@ extern "C" int skr_leiden(skr_ctx* ctx, const skr_mat* rows, const skr_mat* cols
             LAUNCH(refine_apply_kernel, L.n, (const u32*)d_prop, (const u32*)d_target, L.mass, L.n, d_part, d_ptot, d_pcnt, d_small);
             SKR_HIP(hipMemcpyAsync(h_small, d_small, 8, hipMemcpyDeviceToHost, st));
             SKR_HIP(hipStreamSynchronize(st));
+            if (g_trace.on) {  // prop and target are what this round's proposals wrote: the apply kernel only reads them
+                const uint64_t head[5] = {kTraceRefine, (uint64_t)(levels - 1), (uint64_t)L.n, n_blk, n_glb};
+                SKR_TRY(trace_arrays(st, head, 5, d_prop, (size_t)L.n * 4, d_target, (size_t)L.n * 4, h_small[0]));
+            }
             if (h_small[0] == 0) break;
         }
         have_parts = true;
@@ -887,6 +963,10 @@ extern "C" int skr_leiden(skr_ctx* ctx, const skr_mat* rows, const skr_mat* cols
                     const Propose P{d_comm, d_tot, d_cnt, nullptr, nullptr, d_prop, d_pgain, 0, levels > 1};
                     SKR_TRY(propose(P));
                     proposed = true;
+                    if (g_trace.on) {
+                        const uint64_t head[5] = {kTracePropose, (uint64_t)(levels - 1), (uint64_t)L.n, n_blk, n_glb};
+                        SKR_TRY(trace_arrays(st, head, 5, d_prop, (size_t)L.n * 4, d_pgain, (size_t)L.n * 8, 0));
+                    }
                 }
                 if (tries > kSubsetTries) {
                     SKR_HIP(hipMemsetAsync(d_small + 2, 0, 8, st));
@@ -902,6 +982,12 @@ extern "C" int skr_leiden(skr_ctx* ctx, const skr_mat* rows, const skr_mat* cols
                 double q_try = 0.0;
                 sweeps_run++;
                 SKR_TRY(measure(d_comm_try, d_tot_try, d_cnt_try, &moves, &q_try, &used_try));
+                if (g_trace.on) {
+                    const bool kept = moves > 0 && (q_try > q_cur || (q_try == q_cur && used_try < used_cur));
+                    uint64_t rec[kTraceWords] = {kTraceSweep, (uint64_t)(levels - 1), (uint64_t)tries, moves, 0, used_try, kept ? 1u : 0u, 0};
+                    memcpy(&rec[4], &q_try, 8);
+                    g_trace.words.insert(g_trace.words.end(), rec, rec + kTraceWords);
+                }
                 if (moves == 0 && tries == 0) {  // nobody wants to move
                     quiet = true;
                     break;

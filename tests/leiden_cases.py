@@ -271,3 +271,130 @@ PLANTED_CASES = {
     "p300": lambda: planted(300, 30, 0.9, 0.01, 22),
     "p2000": lambda: planted(2000, 40, 0.4, 0.005, 23),
 }
+
+
+# ------------------------------------------------------------------------------------------------ trace cases
+# The graphs whose every proposal pass is pinned (tests/leiden_model.py, tests/golden/leiden_trace.json).  All weights are
+# k / 1024 with k an integer in [1, 4096]: every float64 sum of them is exact in any order and so is their fixed-point
+# form, so the total weight of the model cannot differ from the device's.
+def _grid_weights(rng, count, lo=1, hi=4096):
+    return rng.integers(lo, hi + 1, size=count).astype(np.float64) / 1024.0
+
+
+def _from_arrays(r, c, w, n):
+    r, c = np.asarray(r, dtype=np.int64), np.asarray(c, dtype=np.int64)
+    lo, hi = np.minimum(r, c), np.maximum(r, c)
+    order = np.lexsort((hi, lo))
+    assert len(np.unique(lo * n + hi)) == len(lo) and (lo < hi).all(), "a duplicate pair or a self-loop"
+    return lo[order].astype(np.uint32), hi[order].astype(np.uint32), np.asarray(w, dtype=np.float32)[order], int(n)
+
+
+def trace_dense(n=300, groups=3, p_in=0.9, p_out=0.45, seed=32):
+    """Every node of the planted part has a degree between the two work-unit limits, with many edges to every label; node
+    n has exactly 64 neighbours and node n + 1 exactly 65 (the boundary of the one-wave unit, on tables that accumulate)."""
+    rng = np.random.default_rng(seed)
+    r, c = np.triu_indices(n, 1)
+    same = (r % groups) == (c % groups)
+    keep = rng.random(len(r)) < np.where(same, p_in, p_out)
+    r, c = r[keep], c[keep]
+    w = _grid_weights(rng, len(r))
+    extra_r, extra_c = [], []
+    for node, degree in ((n, 64), (n + 1, 65)):
+        extra_r.append(np.sort(rng.choice(n, size=degree, replace=False)))
+        extra_c.append(np.full(degree, node))
+    r, c = np.concatenate([r] + extra_r), np.concatenate([c] + extra_c)
+    w = np.concatenate([w, _grid_weights(rng, 64 + 65)])
+    return _from_arrays(r, c, w, n + 2)
+
+
+def trace_wide(clusters=3, cliques=90, seed=32, bridges=40):
+    """clusters x cliques four-cliques; inside a cluster one weak edge between each pair of cliques, between clusters a
+    few weak edges.  Level 0 stays in the one-wave unit; the aggregate of the cliques has cliques - 1 neighbours and a
+    self-loop entry."""
+    rng = np.random.default_rng(seed)
+    r, c, w = [], [], []
+    n = clusters * cliques * 4
+    for q in range(clusters * cliques):
+        for a, b in clique_pairs(range(4 * q, 4 * q + 4)):
+            r.append(a), c.append(b), w.append(int(rng.integers(3072, 4097)))
+    for cl in range(clusters):
+        base = cl * cliques
+        for a in range(cliques):
+            for b in range(a + 1, cliques):
+                r.append(4 * (base + a) + int(rng.integers(4))), c.append(4 * (base + b) + int(rng.integers(4)))
+                w.append(int(rng.integers(1, 513)))
+    seen = set()
+    while len(seen) < bridges:
+        a, b = int(rng.integers(n)), int(rng.integers(n))
+        if a // (4 * cliques) != b // (4 * cliques) and (min(a, b), max(a, b)) not in seen:
+            seen.add((min(a, b), max(a, b)))
+    for a, b in sorted(seen):
+        r.append(a), c.append(b), w.append(int(rng.integers(1, 65)))
+    return _from_arrays(r, c, np.asarray(w, dtype=np.float64) / 1024.0, n)
+
+
+def trace_hubs(groups=6, per=400, hubs=12, p_in=0.03, p_out=0.002, cover=0.9, magnet=24, seed=33, exact=(2048, 2049)):
+    """groups x per sparse nodes in planted groups (contiguous blocks of `per`), `hubs` hubs, each tied to about `cover` of
+    the sparse nodes by weights up to 0.5, and a magnet: the last `magnet` sparse nodes, a heavy clique with no other
+    sparse neighbour, to which every hub is tied by weights in (2, 3].  One edge of each hub weighs the full 4.0 (its
+    decoy): the hub first joins that neighbour and moves again when the magnet has gathered, so the sums of its table
+    decide a move.  The magnet's labels are the largest in use and every hub's last CSR entry is a magnet node.  The first
+    len(exact) hubs have exactly those degrees: the boundary of the LDS-table unit, on tables that accumulate."""
+    rng = np.random.default_rng(seed)
+    n_s = groups * per
+    rest = n_s - magnet
+    r, c = np.triu_indices(rest, 1)
+    same = (r // per) == (c // per)
+    keep = rng.random(len(r)) < np.where(same, p_in, p_out)
+    r, c = r[keep], c[keep]
+    w = np.where(same[keep], rng.integers(2048, 4097, size=len(r)), rng.integers(1, 1025, size=len(r)))
+    mr, mc = np.triu_indices(magnet, 1)
+    rs, cs, ws = [r, rest + mr], [c, rest + mc], [w, rng.integers(3072, 4097, size=len(mr))]
+    for h in range(hubs):
+        degree = exact[h] if h < len(exact) else int(rng.binomial(rest, cover)) + magnet
+        nb = np.concatenate([np.sort(rng.choice(rest, size=degree - magnet, replace=False)), np.arange(rest, n_s)])
+        wh = np.concatenate([rng.integers(1, 513, size=degree - magnet), rng.integers(2049, 3073, size=magnet)])
+        wh[int(rng.integers(degree - magnet))] = 4096
+        rs.append(nb), cs.append(np.full(degree, n_s + h)), ws.append(wh)
+    return _from_arrays(np.concatenate(rs), np.concatenate(cs), np.concatenate(ws).astype(np.float64) / 1024.0, n_s + hubs)
+
+
+def trace_many_hubs(hubs=520, leaves=2200, degree=2100, groups=4, seed=34):
+    """`hubs` nodes of degree `degree` > 2 048 over `leaves` leaves: more nodes of the device-memory unit than it has
+    tables, so every workgroup takes several and clears its table between them.  A hub's edges into its own group
+    (h % groups; leaf v: v % groups) are heavy, the others light."""
+    rng = np.random.default_rng(seed)
+    rs, cs, ws = [], [], []
+    for h in range(hubs):
+        nb = np.sort(rng.choice(leaves, size=degree, replace=False))
+        mine = (nb % groups) == (h % groups)
+        rs.append(nb), cs.append(np.full(degree, leaves + h))
+        ws.append(np.where(mine, rng.integers(2048, 4097, size=degree), rng.integers(1, 513, size=degree)).astype(np.float64) / 1024.0)
+    return _from_arrays(np.concatenate(rs), np.concatenate(cs), np.concatenate(ws), leaves + hubs)
+
+
+def trace_pairs_glb(pairs=2100, groups=3, seed=35):
+    """`pairs` strongly tied pairs and one weak edge between every two pairs — heavier inside a planted group (contiguous
+    blocks of pairs, so that the last group holds the largest labels).  No node of level 0 has more than 2 048 entries; every aggregate of a pair has pairs - 1 neighbours and
+    a self-loop entry: the single reserved table of the device-memory unit."""
+    rng = np.random.default_rng(seed)
+    a, b = np.triu_indices(pairs, 1)
+    per = -(-pairs // groups)
+    same = (a // per) == (b // per)
+    r, c = 2 * a + rng.integers(0, 2, size=len(a)), 2 * b + rng.integers(0, 2, size=len(a))
+    w = np.where(same, rng.integers(8, 17, size=len(a)), rng.integers(1, 5, size=len(a)))
+    p = np.arange(pairs)
+    r, c = np.concatenate([2 * p, r]), np.concatenate([2 * p + 1, c])
+    w = np.concatenate([np.full(pairs, 4096), w]).astype(np.float64) / 1024.0
+    return _from_arrays(r, c, w, 2 * pairs)
+
+
+TRACE_CASES = {"dense": trace_dense, "wide": trace_wide, "hubs": trace_hubs, "many_hubs": trace_many_hubs, "pairs_glb": trace_pairs_glb}
+TRACE_SMALL = ("dense", "wide", "hubs")  # rerun by the CPU tests; the other two are only pinned
+# the work unit each case is there for: (fault limit, "blk" or "glb", the 0-based level it must be reached and matter at)
+TRACE_ROUTES = {"dense": (64, "blk", 0), "wide": (64, "blk", 1), "hubs": (2048, "glb", 0), "many_hubs": (2048, "glb", 0),
+                "pairs_glb": (2048, "glb", 1)}
+# (algo, resolution) each trace case runs at; the smallest also under the other two functions, CPM at a resolution where
+# something moves (weights reach 4)
+TRACE_RUNS = {name: [("RBConfigurationVertexPartition", 1.0), ("RBERVertexPartition", 1.0)] for name in TRACE_CASES}
+TRACE_RUNS["dense"] = TRACE_RUNS["dense"] + [("ModularityVertexPartition", 1.0), ("CPMVertexPartition", 1.5)]
