@@ -24,6 +24,9 @@
 // wave issues 24 ds_read_b128 and 32*NPROD MFMAs of 16 cycles.  (The 32x32x16 shape has the same
 // LDS bytes per flop but the chip holds a lower clock on it: -13 % measured; see
 // MI355X_MICROARCH.md, DVFS give-back.)
+// Two k loops over that geometry (template parameter LOOP, knob SEEKR_GEMM_LOOP): 1, the default — four phases of 24 MFMAs
+// per k tile, the two wave rows one barrier apart, LDS-DMA in flight across barriers under counted vmcnt
+// (gemm_phased_schedule.hpp); 0 — one barrier per k tile in front of which the next stage is drained.  The same bits.
 // The LDS image is lane-linear (LDS-DMA), so the bank swizzle chunk ^= (row >> 1) & 7 is applied
 // on the source address and again on the read (same involution), as in the fp32 kernel.
 //
@@ -35,6 +38,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "gemm_phased_schedule.hpp"
 
 namespace {
 
@@ -56,6 +60,9 @@ enum { PLAIN = 0, SELF = 1, CROSS = 2, EDGES = 3, LOWER = 4 };
 using EdgeSink = SkrEdgeSink;  // common.hpp
 template <typename T>
 using vec8 = T __attribute__((ext_vector_type(8)));
+
+// phased loop: the 8-row piece of the A tile that wave `wave` stages for unit `unit` of a k tile (gemm_phased_schedule.hpp)
+__device__ __forceinline__ constexpr int phased_a_piece(int wave, int unit) { return (wave >> 2) * 16 + unit * 4 + (wave & 3); }
 
 __device__ __forceinline__ void lds_dma16(const void* gsrc, void* lds_dst_wave_base) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
@@ -141,6 +148,37 @@ __device__ __forceinline__ void mfma_drain() {
     __builtin_amdgcn_sched_barrier(0);
 }
 
+// The operations run_phased_loop (gemm_phased_schedule.hpp) is instantiated with in the kernel: what is staged, read and
+// multiplied comes from the kernel's lambdas; the waits and barriers are these.  Raw s_barrier and counted waits only:
+// __syncthreads() would drain the LDS-DMA in flight (vmcnt(0)).  The sched_barriers pin reads, waits and MFMA clusters
+// to the side of each barrier the schedule puts them on.
+template <class Issue, class Read, class Mfma>
+struct PhasedOps {
+    Issue& issue_;
+    Read& read_;
+    Mfma& mfma_;
+    template <int U>
+    __device__ __forceinline__ void issue(int64_t tile, skr_phased::Int<U> u) { issue_(tile, u); }
+    template <int U>
+    __device__ __forceinline__ void read(int64_t tile, skr_phased::Int<U> u) { read_(tile, u); }
+    template <int U>
+    __device__ __forceinline__ void mfma(skr_phased::Int<U> u) { mfma_(u); }
+    template <int N>
+    __device__ __forceinline__ void wait_vm(skr_phased::Int<N>) {
+        static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+    }
+    __device__ __forceinline__ void barrier() {
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    __device__ __forceinline__ void wait_lgkm() {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+    }
+};
+
 // PERSIST: one workgroup per CU for the whole launch.  Tile slots are handed out by eight counters,
 // one per XCD group (slot i of group x is block id 8 i + x of the order above, so an XCD keeps
 // walking 8 x 4 sub-tiles in its own L2); a workgroup drains the queue of the XCD it runs on
@@ -156,7 +194,9 @@ __device__ __forceinline__ void mfma_drain() {
 // accumulators); a wave then reads 32 instead of 24 fragments per k tile but there are half as many waves: 128 instead of
 // 192 KiB of ds_read per CU and k tile.  With nobody to cover its LDS latency the k loop is software-pipelined by hand
 // (below); per accumulator the products are added in the same order, so r is the same bits.
-template <typename T, int NPROD, int MODE, bool PERSIST, bool DIAG = false, int WAVES = 8>
+// LOOP = 1 (SEEKR_GEMM_LOOP=1, the default; 8 waves, three or four products): the phased k loop — gemm_phased_schedule.hpp has the
+// schedule and its rules, the k loop below the operations.  Everything outside the k loop is the same code.
+template <typename T, int NPROD, int MODE, int LOOP, bool PERSIST, bool DIAG = false, int WAVES = 8>
 __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void pearson_gemm_split16_kernel(
     const T* __restrict__ A, const T* __restrict__ B, float* __restrict__ C, float* __restrict__ Ct,
     int64_t M, int64_t N, int64_t kt, int64_t ldc, int64_t ldct, float kdiv, int64_t tiles_m, int64_t tiles_n,
@@ -170,8 +210,12 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void pearson_gemm_split16_ke
     constexpr bool SYM = MODE == SELF;
     constexpr bool SWAPPED = MODE == LOWER;  // the roles of A and B in the order of the products (comment at the enum)
     static_assert(!SWAPPED || WAVES == 8, "LOWER exists for the 8-wave geometry");
+    static_assert(LOOP == 0 || (LOOP == 1 && WAVES == 8 && NPROD >= 3), "the phased loop: 8-wave geometry, split products");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ int64_t s_bid;
+    // the phased loop keeps LDS-DMA in flight across barriers: its slot word lives behind the stages in the ONE dynamic
+    // array (a second __shared__ object beside it can bring hipcc's vmcnt(0) back in front of the ds_reads)
+    __shared__ int64_t s_bid_static;
+    int64_t& s_bid = LOOP == 1 ? *reinterpret_cast<int64_t*>(smem + 2 * kStageBytes) : s_bid_static;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
@@ -229,6 +273,20 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void pearson_gemm_split16_ke
         a_voff[p] = (uint32_t)(ra * pitch * 2 + chunk * 16);
         b_voff[p] = (uint32_t)(rb * pitch * 2 + chunk * 16);
     }
+    if constexpr (LOOP == 1) {
+        // phased loop: A piece p of this wave is its piece of unit p of a k tile (gemm_phased_schedule.hpp) — 8 of the
+        // rows of row tiles 2p, 2p + 1 of wave row wave / 4; the B pieces are the ones above
+        static_assert(PP == skr_phased::kPhases && PP == skr_phased::kPiecesB, "one A piece per wave and unit, B pieces in unit 0");
+#pragma unroll
+        for (int p = 0; p < PP; p++) {
+            const int row = phased_a_piece(wave, p) * 8 + (lane >> 3);
+            const int chunk = (lane & 7) ^ ((row >> 1) & 7);
+            a_voff[p] = (uint32_t)(std::min<int64_t>(row, M - 1 - row_base) * pitch * 2 + chunk * 16);
+            // computed HERE: left alone, hipcc sinks the eight clamps into each entry of the k loop and keeps their 64-bit
+            // inputs live up to there instead of the eight offsets (three spilled dwords)
+            asm volatile("" : "+v"(a_voff[p]), "+v"(b_voff[p]));
+        }
+    }
     auto stage = [&](int buf, int64_t tile, bool half = false) {  // half: diagnostic only (a timing experiment, below)
         char* abase = smem + buf * kStageBytes;
         char* bbase = abase + TM * kRowBytes;
@@ -271,14 +329,74 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void pearson_gemm_split16_ke
     // phase (no MFMA ever waits on a fresh LDS read) ran in the same 25.1 vs 25.2 ms, so the
     // simple form stays.
     int cur = 0;
-    stage(0, 0);
-    if (WAVES == 4 && kt > 1) stage(1, 1);  // the 4-wave loop keeps two stages in flight (below)
-    __syncthreads();
+    if constexpr (LOOP == 0) {
+        stage(0, 0);
+        if (WAVES == 4 && kt > 1) stage(1, 1);  // the 4-wave loop keeps two stages in flight (below)
+        __syncthreads();
+    }  // the phased loop stages its own prologue
     if (DIAG) st[2] = __builtin_amdgcn_s_memtime();
     const bool no_dma = DIAG && (diag[1] & 1);  // diagnostic only: k loop without its staging traffic (results meaningless)
     const bool same_tile = DIAG && (diag[1] & 2);  // diagnostic only: every stage re-loads k tile 0 (served by the nearest cache)
     const bool two_units = DIAG && (diag[1] & 8);  // diagnostic only: TIMING CEILING of a two-product-unit split (results meaningless)
-    if (DIAG && WAVES == 8 && two_units) {
+    if constexpr (LOOP == 1) {
+        // The phased loop: run_phased_loop (gemm_phased_schedule.hpp) calls the operations below in the order, with the
+        // counts and under the barriers its header states; the waves of wave row 1 run one barrier behind the others.
+        // Per accumulator the products enter as in the loop below — lo x hi, hi x lo, hi x hi, k tiles ascending — so r
+        // is the same bits.  Rows differ by multiples of 16, so one swizzle term serves all fragments of an operand half.
+        using skr_phased::Int;
+        const int a_lane_hi = a_off[0] + ((q ^ a_swz[0]) << 4), a_lane_lo = a_off[0] + (((4 + q) ^ a_swz[0]) << 4);
+        const int b_lane_hi = b_off[0] + ((q ^ b_swz[0]) << 4), b_lane_lo = b_off[0] + (((4 + q) ^ b_swz[0]) << 4);
+        vec8<T> bhi[NT], blo[NT], ahi[2], alo[2];
+        auto issue = [&](int64_t tile, auto unit_c) {  // this wave's pieces of unit 4 tile + U: one of A, in unit 0 the B tile's too
+            constexpr int U = decltype(unit_c)::value;
+            char* abase = smem + (int)(tile & 1) * kStageBytes;
+            const uint32_t toff = (uint32_t)tile * kRowBytes;
+            if constexpr (U == 0) {
+#pragma unroll
+                for (int p = 0; p < PP; p++) lds_dma16(b_tile + (b_voff[p] + toff), abase + TM * kRowBytes + (wave * PP + p) * 1024);
+            }
+            lds_dma16(a_tile + (a_voff[U] + toff), abase + phased_a_piece(wave, U) * 1024);
+        };
+        auto read = [&](int64_t tile, auto unit_c) {
+            constexpr int U = decltype(unit_c)::value;
+            const char* base = smem + (int)(tile & 1) * kStageBytes;
+            if constexpr (U == 0) {
+#pragma unroll
+                for (int i = 0; i < NT; i++) {
+                    bhi[i] = *reinterpret_cast<const vec8<T>*>(base + b_lane_hi + i * 16 * kRowBytes);
+                    blo[i] = *reinterpret_cast<const vec8<T>*>(base + b_lane_lo + i * 16 * kRowBytes);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 2; i++) {
+                ahi[i] = *reinterpret_cast<const vec8<T>*>(base + a_lane_hi + (2 * U + i) * 16 * kRowBytes);
+                alo[i] = *reinterpret_cast<const vec8<T>*>(base + a_lane_lo + (2 * U + i) * 16 * kRowBytes);
+            }
+        };
+        auto mfma = [&](auto unit_c) {
+            constexpr int U = decltype(unit_c)::value;
+            __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+#pragma unroll
+                for (int nt = 0; nt < NT; nt++) {
+                    f32x4v& c = acc[2 * U + i][nt];
+                    if (NPROD >= 4) c = mfma16x16(alo[i], blo[nt], c);
+                    if (SWAPPED) {
+                        c = mfma16x16(ahi[i], blo[nt], c);
+                        c = mfma16x16(alo[i], bhi[nt], c);
+                    } else {
+                        c = mfma16x16(alo[i], bhi[nt], c);
+                        c = mfma16x16(ahi[i], blo[nt], c);
+                    }
+                    c = mfma16x16(ahi[i], bhi[nt], c);
+                }
+            __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        PhasedOps<decltype(issue), decltype(read), decltype(mfma)> ops{issue, read, mfma};
+        skr_phased::run_phased_loop(ops, kt, wm == 1);
+    } else if (DIAG && WAVES == 8 && two_units) {
         // VERDICT r3 #5, measured before anything is built around it: the two cross products (lo x hi, hi x lo: two
         // 16-bit MFMAs per k tile and accumulator tile) replaced by ONE v_mfma_i32_16x16x64_i8 — the cycles of one 16-bit
         // MFMA (MI355X_MICROARCH.md: I8 16x16x64 = the cycles of the BF16 form at twice the K) — fed with the bytes of
@@ -945,7 +1063,14 @@ int launch_chunk(skr_ctx* ctx, const T* Ac, const T* Bc, const SplitOut& o, int6
     if (ctx->knobs.gemm_persist && slots > ctx->num_cu) {
         uint32_t* queues = ctx->d_flags + 8;  // eight counters, zeroed per launch
         SKR_HIP(hipMemsetAsync(queues, 0, 8 * sizeof(uint32_t), ctx->stream));
-        auto kern = pearson_gemm_split16_kernel<T, NPROD, MODE, true>;
+        auto kern = pearson_gemm_split16_kernel<T, NPROD, MODE, 0, true>;
+        size_t lds = 2 * kStageBytes;
+        if constexpr (NPROD >= 3) {
+            if (ctx->knobs.gemm_loop == 1) {  // SEEKR_GEMM_LOOP=1: the phased k loop; its slot word lives behind the stages
+                kern = pearson_gemm_split16_kernel<T, NPROD, MODE, 1, true>;
+                lds = 2 * kStageBytes + 16;
+            }
+        }
         unsigned long long* diag = nullptr;
 #ifdef SEEKR_DIAG
         // libseekr_hip_diag.so only (python -m seekr_amd.build --diag; tools/gemm_diag.py): the production library holds
@@ -963,7 +1088,14 @@ int launch_chunk(skr_ctx* ctx, const T* Ac, const T* Bc, const SplitOut& o, int6
             // 7 = no epilogue stores at all (timing ceiling of hiding the epilogue: round 6)
             if (dmode >= 2 && dmode <= 7)
                 SKR_HIP(hipMemsetAsync(diag + 1, dmode == 2 ? 1 : (dmode == 3 ? 2 : (dmode == 4 ? 4 : (dmode == 5 ? 8 : (dmode == 6 ? 16 : 32)))), 1, ctx->stream));
-            kern = pearson_gemm_split16_kernel<T, NPROD, (MODE == SELF ? SELF : PLAIN), true, true>;
+            kern = pearson_gemm_split16_kernel<T, NPROD, (MODE == SELF ? SELF : PLAIN), 0, true, true>;
+            lds = 2 * kStageBytes;
+            if constexpr (NPROD == 3) {
+                if (ctx->knobs.gemm_loop == 1 && dmode == 1) {  // the stamps around the phased loop (the experiments are the present loop's)
+                    kern = pearson_gemm_split16_kernel<T, NPROD, (MODE == SELF ? SELF : PLAIN), 1, true, true>;
+                    lds = 2 * kStageBytes + 16;
+                }
+            }
         }
 #endif
         unsigned threads = 512;
@@ -971,21 +1103,25 @@ int launch_chunk(skr_ctx* ctx, const T* Ac, const T* Bc, const SplitOut& o, int6
         if constexpr (NPROD == 3 && MODE != LOWER) {
             // A/B arm (libseekr_hip_diag.so only; measured 13 % slower): 4 waves x 128 x 128 (kernel comment)
             if (ctx->knobs.gemm_wave_tile == 1 && !diag) {
-                kern = pearson_gemm_split16_kernel<T, NPROD, MODE, true, false, 4>;
+                kern = pearson_gemm_split16_kernel<T, NPROD, MODE, 0, true, false, 4>;
                 threads = 256;
+                lds = 2 * kStageBytes;
             }
         }
 #endif
-        SKR_TRY(skr_kernel_lds(ctx, reinterpret_cast<const void*>(kern), 2 * kStageBytes));
+        SKR_TRY(skr_kernel_lds(ctx, reinterpret_cast<const void*>(kern), lds));
         // A resident workgroup owns its CU outright (8 waves x ~248 VGPRs, 128 KiB LDS): with RCCL traffic
         // in flight on the communication stream a few CUs are left free, or the send/recv kernels of
         // shift s+1 could not start before this launch ends and the overlap of §5 would be lost.
         const int reserve = ctx->knobs.gemm_reserve_cus >= 0 ? ctx->knobs.gemm_reserve_cus : (ctx->nranks > 1 ? 8 : 0);
         const unsigned grid = (unsigned)std::max(8, ctx->num_cu - reserve);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), 2 * kStageBytes, ctx->stream, Ac, Bc, o.C, o.Ct, M, N, ktc, o.ldc, o.ldct, K,
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, ctx->stream, Ac, Bc, o.C, o.Ct, M, N, ktc, o.ldc, o.ldct, K,
                            tiles_m, tiles_n, super_n, queues, slots / 8, kt_pitch, accumulate | ((ctx->knobs.gemm_epilogue & 3) << 2) | (ctx->knobs.gemm_subtile << 8), diag, es);
     } else {
-        auto kern = pearson_gemm_split16_kernel<T, NPROD, MODE, false>;
+        auto kern = pearson_gemm_split16_kernel<T, NPROD, MODE, 0, false>;
+        if constexpr (NPROD >= 3) {
+            if (ctx->knobs.gemm_loop == 1) kern = pearson_gemm_split16_kernel<T, NPROD, MODE, 1, false>;
+        }
         SKR_TRY(skr_kernel_lds(ctx, reinterpret_cast<const void*>(kern), 2 * kStageBytes));
         hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(512), 2 * kStageBytes, ctx->stream, Ac, Bc, o.C, o.Ct, M, N, ktc, o.ldc,
                            o.ldct, K, tiles_m, tiles_n, super_n, (uint32_t*)nullptr, (int64_t)0, kt_pitch,

@@ -97,6 +97,7 @@ def main():
         ts = np.array(ts[1:])
         med = float(np.median(ts))
         units = 2 if name == "f16f8" else 3
+        print("%-16s rounds (ms, the first dropped): %s  max %.3f" % (name, " ".join("%.3f" % t for t in ts), ts.max()))
         print("%-16s median %.3f ms  min %.3f ms  -> %.1f G pairs/s delivered, MFMA executed %.0f TF in 16-bit product-units (%.3f of 2.5 PF)"
               % (name, med, ts.min(), pairs / med / 1e6, units * 2 * args.cols * mult / med / 1e9, units * 2 * args.cols * mult / med / 1e9 / 2500))
 

@@ -31,6 +31,7 @@ ap.add_argument("--two-units", action="store_true", help="TIMING CEILING of a tw
 ap.add_argument("--half-x", action="store_true", help="f16f8 operands; TIMING CEILING of an H / X layout whose X line carries lo8 alone (staged half); r is garbage.  Printed next to a stamps-only launch of the f16f8 kernel")
 ap.add_argument("--no-mirror", action="store_true", help="self mode without the mirror stores (timing experiment; the lower triangle stays unwritten)")
 ap.add_argument("--no-stores", action="store_true", help="NO epilogue store at all (round 6): the timing ceiling of hiding the epilogue under the next tile's k loop; r stays unwritten.  Printed next to a stamps-only launch of the same process")
+ap.add_argument("--loops", action="store_true", help="the present k loop (SEEKR_GEMM_LOOP=0) and the phased one (=1), stamps only, alternated three times in this process")
 args = ap.parse_args()
 ctx = _lib.default_context()
 rng = np.random.default_rng(0)
@@ -101,6 +102,16 @@ elif args.no_stores:
         a_ms = one_launch(1, "as shipped (stamps only)")
         b_ms = one_launch(7, "no epilogue stores (timing ceiling)")
         print("==== launch %.3f -> %.3f ms: %+.1f %%" % (a_ms, b_ms, (b_ms / a_ms - 1) * 100))
+elif args.loops:
+    for rep in range(3):
+        ms = []
+        for val, label in (("0", "present k loop (stamps only)"), ("1", "phased k loop (stamps only)")):
+            os.environ["SEEKR_GEMM_LOOP"] = val
+            ctx.reload_knobs()
+            ms.append(one_launch(1, label))
+        os.environ.pop("SEEKR_GEMM_LOOP")
+        ctx.reload_knobs()
+        print("==== launch %.3f -> %.3f ms: %+.1f %%" % (ms[0], ms[1], (ms[1] / ms[0] - 1) * 100))
 elif mode == 5:
     for rep in range(3):  # alternate in one process: stamps only / two product-units
         a_ms = one_launch(1, "three product-units (shipped arithmetic, stamps only)")
