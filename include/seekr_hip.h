@@ -526,6 +526,31 @@ int skr_topk_merge_rows(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t c
  * buffer and the list are sorted together before a sweep step of 1 024 cells that might not fit).  Either may be NULL. */
 int skr_topk_merge_limits(int* kmax, int* candidate_cap);
 
+/* ---------------------------------------------------------------- the k-mers behind a similarity -- */
+/* r[i, j] is the mean over the columns w of z1[i, w] * z2[j, w]; this lists, for each of n_pairs pairs (rows[e], cols[e])
+ * (SKR_U32 vectors), the `top` columns whose term c[w] = float32(z1[rows[e], w] * z2[cols[e], w]) is largest (largest != 0)
+ * or smallest (largest = 0: the order of -c), in skr_topk_merge_rows' order: value descending, -0 == +0, NaN after every
+ * number, ties to the smaller column — np.argsort(-key, kind="stable")[:top] with key = c or -c.  z1 [N1, W] and z2 [N2, W]
+ * are SKR_F32 (z2 may be z1; row views are fine), W >= 1.  Pair e's list is at e * top of every output: out_idx (SKR_U32)
+ * the column, out_val (SKR_F32) c's own bits (never the negated ones), out_z1 / out_z2 (SKR_F32, either may be NULL) the
+ * two factors; slots beyond W columns hold 0xFFFFFFFF / NaN (0x7FC00000).  Both rows are read once whatever `top` is, and
+ * no product is written to memory.  1 <= top <= kmax of skr_topk_merge_limits.  A pair with rows[e] >= N1 or cols[e] >= N2
+ * is never dereferenced: its slots are padded, the call returns SKR_ERR_INVALID and *first_bad (may be NULL; -1
+ * otherwise) is the first such pair.  The call waits for the device.                                                   */
+int skr_pair_kmers(skr_ctx* ctx, const skr_mat* z1, const skr_mat* z2, const skr_mat* rows, const skr_mat* cols,
+                   int64_t n_pairs, int top, int largest, skr_mat* out_idx, skr_mat* out_val, skr_mat* out_z1,
+                   skr_mat* out_z2, int64_t* first_bad);
+/* Column means and sample standard deviations of groups of rows of x (SKR_F32 [N, W]) in numpy's own float32 chains for
+ * np.mean(x[sel], axis=0) and np.std(x[sel], axis=0, ddof=1).  order (SKR_U32) lists row ids group after group; group g
+ * owns order[starts[g] : starts[g + 1]] (starts: n_groups + 1 HOST values, non-decreasing), n its size.  Per column:
+ * acc = +0, then acc = fl32(acc + x[i, j]) row after row in the list's order; mean = fl32(acc / fl32(n));
+ * d = fl32(x[i, j] - mean), acc2 the same chain over fl32(d * d); sd = sqrt_rn(fl32(acc2 / fl32(n - 1))) — NaN for
+ * n = 1; an empty group gives NaN in both; every NaN result is written as the quiet NaN 0x7FC00000.  mean, sd (may be
+ * NULL): SKR_F32, at least n_groups * W cells, group g at g * W.  An entry of order >= N is never dereferenced and the
+ * call returns SKR_ERR_INVALID naming the first one.  The call waits for the device.                               */
+int skr_group_colstat(skr_ctx* ctx, const skr_mat* x, const skr_mat* order, const int64_t* starts, int64_t n_groups,
+                      skr_mat* mean, skr_mat* sd);
+
 /* ---------------------------------------------------------------- communities (Leiden) -- */
 /* Communities of an undirected weighted graph (the step kmer_leiden.py:131-146 hands to leidenalg.find_partition), on the
  * device: local moving, refinement and aggregation, level after level (seekr_amd/csrc/leiden.hip, DESIGN_KERNELS.md).

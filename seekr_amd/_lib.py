@@ -131,6 +131,8 @@ SIGNATURES = {
     "skr_topk_rows": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _int, _p, _p]),
     "skr_topk_merge_rows": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _p, _p, C.POINTER(_int)]),
     "skr_topk_merge_limits": (_int, [C.POINTER(_int), C.POINTER(_int)]),
+    "skr_pair_kmers": (_int, [_p, _p, _p, _p, _p, _i64, _int, _int, _p, _p, _p, _p, C.POINTER(_i64)]),
+    "skr_group_colstat": (_int, [_p, _p, _p, _p, _i64, _p, _p]),
     "skr_leiden": (_int, [_p, _p, _p, _p, _i64, _i64, _int, C.c_double, _int, _int, _p, C.POINTER(C.c_double), C.POINTER(_i64),
                           C.POINTER(_i64)]),
     "skr_leiden_last": (_int, [C.POINTER(_int), C.POINTER(_i64)]),
@@ -1157,6 +1159,33 @@ def topk_merge_rows(ctx, r, idx, val, k, first, nrows=None, col_begin=0, col_end
                                     1 if exclude_diag else 0, int(k), 1 if first else 0, idx._h, val._h,
                                     C.byref(nan) if want_nan else None))
     return bool(nan.value)
+
+
+class BadIndex(ValueError):
+    """An index list names a row outside its matrix; `first_bad` is the position of the first such entry."""
+
+    def __init__(self, message, first_bad):
+        super().__init__(message)
+        self.first_bad = int(first_bad)
+
+
+def pair_kmers(ctx, z1, z2, rows, cols, n_pairs, top, largest, out_idx, out_val, out_z1=None, out_z2=None):
+    """skr_pair_kmers: for each pair (rows[e], cols[e]) the `top` columns with the largest (smallest: largest=False)
+    z1[rows[e], w] * z2[cols[e], w] into row e (e * top) of out_idx / out_val / out_z1 / out_z2.  BadIndex when a pair
+    names a row outside z1 / z2 (checked on the device; nothing of such a pair is read)."""
+    bad = _i64(-1)
+    rc = lib().skr_pair_kmers(ctx._h, z1._h, z2._h, rows._h, cols._h, int(n_pairs), check_topk_k(top, "top"),
+                              1 if largest else 0, out_idx._h, out_val._h, _h(out_z1), _h(out_z2), C.byref(bad))
+    if rc == -1 and bad.value >= 0:
+        raise BadIndex(lib().skr_last_error().decode("utf-8", "replace"), bad.value)
+    check(rc)
+
+
+def group_colstat(ctx, x, order, starts, mean, sd=None):
+    """skr_group_colstat: np.mean / np.std(ddof=1) along axis 0 of the rows order[starts[g] : starts[g + 1]] of x, group
+    after group, in numpy's float32 chains, into row g of mean / sd.  `starts`: host integers, one more than groups."""
+    starts = np.ascontiguousarray(starts, dtype=np.int64)
+    check(lib().skr_group_colstat(ctx._h, x._h, order._h, starts.ctypes.data_as(_p), len(starts) - 1, mean._h, _h(sd)))
 
 
 # ----------------------------------------------------------------------------- writers -----

@@ -15,7 +15,7 @@ LIB = os.path.join(HERE, "libseekr_hip.so")
 DIAG_LIB = os.path.join(HERE, "libseekr_hip_diag.so")
 DIAG_SOURCES = ["pearson_bf16.hip"]  # compiled a second time with -DSEEKR_DIAG for the diagnostic library
 SOURCES = ["ctx.hip", "pack.hip", "count.hip", "windows.hip", "normalize.hip", "normalize_any.hip", "pearson.hip", "pearson_bf16.hip", "operand.hip",
-           "consumers.hip", "cells.hip", "topk.hip", "fused_edges.hip", "adjust.hip", "leiden.hip", "comm.hip", "io.hip", "csv_read.hip", "host_api.hip"]
+           "consumers.hip", "cells.hip", "topk.hip", "explain.hip", "fused_edges.hip", "adjust.hip", "leiden.hip", "comm.hip", "io.hip", "csv_read.hip", "host_api.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-I" + os.path.join(HERE, "..", "include")]
@@ -26,6 +26,7 @@ PER_FILE = {
     "count.hip": ["-ffp-contract=off"],
     "windows.hip": ["-ffp-contract=off"],
     "adjust.hip": ["-ffp-contract=off"],
+    "explain.hip": ["-ffp-contract=off"],  # acc + d * d is two roundings, as in numpy's chains
     "leiden.hip": ["-ffp-contract=off"],  # the gains of every work unit are the same float64 expression, term by term
     # the 4-wave geometry of the contraction has 64 accumulator tiles per lane: its epilogue loops are only unrolled (and
     # the accumulator array only kept in registers) above clang's default 16 384-instruction limit for `#pragma unroll`

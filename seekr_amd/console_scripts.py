@@ -2,8 +2,9 @@
 (console_scripts.py:564-681, 887-918), and `seekr_domain_pearson` (sliding windows of a target against queries: no
 counterpart in the reference), `seekr_nearest` (the k most correlated rows of every row: likewise) and
 `seekr_significant_pairs` (the pairs whose corrected p-value is at most alpha, without any N x N matrix: likewise), and
-`seekr_kmer_leiden` with the reference's flags (console_scripts.py:1033-1101) plus --edges.  Only the commands on the hot
-path are provided."""
+`seekr_kmer_leiden` with the reference's flags (console_scripts.py:1033-1101) plus --edges and --kmers_top, and
+`seekr_pair_kmers` (the k-mers behind the similarity of listed pairs: no counterpart).  Only the commands on the hot path
+are provided."""
 import argparse
 import sys
 
@@ -412,6 +413,77 @@ def console_domain_significant():
                             float(args.alpha))
 
 
+PAIR_KMERS_DOC = """
+Description
+-----------
+The k-mers behind a similarity: for every pair of a pair list (what seekr_significant_pairs or seekr_nearest writes) the
+k-mers whose z-score product contributes most to the pair's Pearson correlation, computed on an MI355X from the count
+file(s) the list was made from.  r of a pair is the mean of these products over all k-mers.  The output is a CSV with
+the columns row,col,rank,kmer,contribution,z_row,z_col: rank 0 is the largest contribution (--smallest: the most
+negative one).  K-mer names come from the header of the labelled count file; with -bi they are the words over the
+alphabet (-a) of length -k in counting order.
+
+Examples
+--------
+    ten k-mers per significant pair:   seekr_pair_kmers counts.csv pairs.csv -t 10 -o pair_kmers.csv
+    neighbours across two .npy files:  seekr_pair_kmers a.npy b.npy nearest.csv -bi -k 6 -o pair_kmers.csv
+"""
+
+
+def _run_pair_kmers(counts, counts2, pairs, top, outfile, binary_input, kmer, alphabet, smallest):
+    import csv
+    from itertools import product
+    from seekr_amd import explain
+    names = names2 = None
+    if binary_input:
+        counts = np.load(counts)
+        counts2 = None if counts2 is None else np.load(counts2)
+        kmers = ["".join(t) for t in product(alphabet, repeat=kmer)]
+    else:
+        kmers = _csv_column_labels(counts)
+        counts, names = _read_labelled_csv(counts)
+        counts2, names2 = (None, names) if counts2 is None else _read_labelled_csv(counts2)
+    if len(kmers) != np.shape(counts)[1]:
+        raise ValueError("{} k-mer names for {} columns: -k and -a must be those the counts were made with".format(
+            len(kmers), np.shape(counts)[1]))
+    rows, cols = explain.read_pairs_csv(pairs, names, names2)
+    res = explain.pair_kmers(counts, rows, cols, counts2=counts2, top=top, largest=not smallest, kmers=kmers)
+    with open(outfile, "w", newline="") as f:
+        out = csv.writer(f, lineterminator="\n")
+        out.writerow(["row", "col", "rank", "kmer", "contribution", "z_row", "z_col"])
+        for e, words in enumerate(res.words()):
+            i, j = int(rows[e]), int(cols[e])
+            for t, word in enumerate(words):
+                out.writerow([i if names is None else names[i], j if names2 is None else names2[j], t, word,
+                              str(res.contribution[e, t]), str(res.z_row[e, t]), str(res.z_col[e, t])])
+
+
+def _csv_column_labels(path):
+    """The column labels of a labelled count file (its header line without the index cell)."""
+    import csv
+    with open(path, newline="") as f:
+        return next(csv.reader(f))[1:]
+
+
+def console_pair_kmers():
+    parser = argparse.ArgumentParser(usage=PAIR_KMERS_DOC, formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    parser.add_argument("files", nargs="+", metavar="counts [counts2] pairs.csv",
+                        help="Count file of the rows, optionally the count file of the columns, then the pair list.")
+    parser.add_argument("-t", "--top", default=10, help="K-mers per pair (at most %d)." % _lib.TOPK_MERGE_KMAX)
+    parser.add_argument("-o", "--outfile", default="pair_kmers.csv",
+                        help="Where the list goes (CSV: row,col,rank,kmer,contribution,z_row,z_col).")
+    parser.add_argument("-bi", "--binary_input", action="store_true", help="The count files are .npy, not labelled CSV.")
+    parser.add_argument("-k", "--kmer", default=6, help="With -bi: the word length the counts were made with.")
+    parser.add_argument("-a", "--alphabet", default="AGTC", help="With -bi: the alphabet the counts were made with.")
+    parser.add_argument("--smallest", action="store_true", help="List the most negative contributions instead.")
+    args = _parse_args_or_exit(parser)
+    if len(args.files) not in (2, 3):
+        parser.error("expected: counts [counts2] pairs.csv")
+    counts, counts2, pairs = (args.files[0], None, args.files[1]) if len(args.files) == 2 else args.files
+    _run_pair_kmers(counts, counts2, pairs, int(args.top), args.outfile, args.binary_input, int(args.kmer), args.alphabet,
+                    args.smallest)
+
+
 KMER_LEIDEN_DOC = """
 Description
 -----------
@@ -449,7 +521,9 @@ def console_kmer_leiden():
                         help="name and path of the nodes and edges csv files; _nodes_leiden.csv and _edges_leiden.csv are appended.")
     parser.add_argument("--edges", default="all", choices=["all", "nonzero"],
                         help="edges file: every upper-triangle cell, zeros included (the reference), or the kept edges only.")
+    parser.add_argument("-kt", "--kmers_top", default=None,
+                        help="with --csvfile: also write _kmers_leiden.csv, this many top k-mers (by mean count) per community.")
     args = _parse_args_or_exit(parser)
     kmer_leiden.kmer_leiden(args.fasta, args.mean_path, args.std_path, int(args.kmer), args.algo, float(args.rs), float(args.pearsoncutoff),
                             args.setseed, args.edgecolormethod, float(args.edgethreshold), int(args.labelfontsize), args.plotname,
-                            args.csvfile, edges=args.edges)
+                            args.csvfile, edges=args.edges, kmers_top=None if args.kmers_top is None else int(args.kmers_top))

@@ -25,6 +25,7 @@ setup(
             # the windows of a target each query is significantly similar to (no counterpart either)
             "seekr_domain_significant = seekr_amd.console_scripts:console_domain_significant",
             "seekr_kmer_leiden = seekr_amd.console_scripts:console_kmer_leiden",
+            "seekr_pair_kmers = seekr_amd.console_scripts:console_pair_kmers",
         ]
     },
 )
