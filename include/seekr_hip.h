@@ -472,6 +472,30 @@ int skr_select_cells_ge(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t c
  * allocation: SKR_ERR_INVALID.                                                                                     */
 int skr_vec_copy(skr_ctx* ctx, const skr_mat* src, int64_t src_off, skr_mat* dst, int64_t dst_off, int64_t count);
 
+/* How the cells of the float32 block r[0:nrows, col_begin:col_end] are distributed: counts ADDED into host arrays of
+ * uint64_t the caller owns (a run over many blocks accumulates; the device keeps nothing between calls; the calls wait
+ * for the device).  Every cell is counted — no zero rule, no diagonal rule; with upper_only != 0 only the cells whose
+ * global column (col_global0 + j, j = r's own column index) is greater than their global row (row_global0 + i), as in
+ * skr_edges.  A NaN cell of either sign bit adds one to *nan and to no bin.  The counts are integers: the same input
+ * gives the same numbers.  Tiled as skr_select_cells_ge (one row x 1 024 columns, aligned 16-byte loads); each
+ * workgroup counts in LDS (uint32) and adds its non-zero bins to 64-bit counters, so a block may hold 2^32 cells or more.
+ *
+ * skr_hist_key_digits: key(v) = the uint32 whose order is the order of the values, -0 just below +0 (the float's bits
+ * with the sign bit set for v >= +0, all bits inverted otherwise).  A cell whose top prefix_bits key bits equal
+ * prefixes[q] adds one to hist[(q << bits) + ((key >> shift) & (2^bits - 1))]; prefix_bits = 0 (then n_prefixes = 1,
+ * prefixes[0] ignored) is one histogram of every cell.  1 <= bits <= 12, shift + bits <= 32, 0 <= prefix_bits <= 32,
+ * 1 <= n_prefixes <= 8 distinct values below 2^prefix_bits, n_prefixes * 2^bits <= 8 192; else SKR_ERR_INVALID.
+ *
+ * skr_hist_edges: bin b of hist[0 : n_edges - 1] holds edges[b] <= v < edges[b + 1], the last bin also v == edges[n_edges
+ * - 1] (np.histogram's rule); v < edges[0] adds to *below, v > edges[n_edges - 1] to *above (the infinities among them).
+ * edges: 2 ... 4 097 host float32, finite and strictly ascending, else SKR_ERR_INVALID.                              */
+int skr_hist_key_digits(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t col_begin, int64_t col_end,
+                        int64_t row_global0, int64_t col_global0, int upper_only, int shift, int bits, int prefix_bits,
+                        const uint32_t* prefixes, int n_prefixes, uint64_t* hist, uint64_t* nan);
+int skr_hist_edges(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t col_begin, int64_t col_end, int64_t row_global0,
+                   int64_t col_global0, int upper_only, const float* edges, int n_edges, uint64_t* hist, uint64_t* below,
+                   uint64_t* above, uint64_t* nan);
+
 /* The non-zero cells that kmer_leiden.py:94-96 leaves in a block of r, as an edge list and
  * without writing the zeros: cells of r[0:nrows, col_begin:col_end] with !(v < cutoff) (NaN
  * stays, like numpy's mask), v != 0 and global row != global column, where global row =

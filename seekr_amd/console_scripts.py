@@ -2,9 +2,10 @@
 (console_scripts.py:564-681, 887-918), and `seekr_domain_pearson` (sliding windows of a target against queries: no
 counterpart in the reference), `seekr_nearest` (the k most correlated rows of every row: likewise) and
 `seekr_significant_pairs` (the pairs whose corrected p-value is at most alpha, without any N x N matrix: likewise), and
-`seekr_kmer_leiden` with the reference's flags (console_scripts.py:1033-1101) plus --edges and --kmers_top, and
-`seekr_pair_kmers` (the k-mers behind the similarity of listed pairs: no counterpart).  Only the commands on the hot path
-are provided."""
+`seekr_kmer_leiden` with the reference's flags (console_scripts.py:1033-1101) plus --edges, --kmers_top and --density, and
+`seekr_pair_kmers` (the k-mers behind the similarity of listed pairs: no counterpart) and `seekr_r_distribution` (the
+histogram, quantiles and density cutoffs of r without the matrix: likewise).  Only the commands on the hot path are
+provided."""
 import argparse
 import sys
 
@@ -496,6 +497,7 @@ Examples
 --------
     communities at r >= 0.05, CSV files:   seekr_kmer_leiden seqs.fa mean.npy std.npy 4 -pco 0.05 -cf out
     modularity, kept edges only:           seekr_kmer_leiden seqs.fa mean.npy std.npy 6 -a ModularityVertexPartition -cf out --edges nonzero
+    the strongest 0.1 %% of the pairs:     seekr_kmer_leiden seqs.fa mean.npy std.npy 6 -d 0.001 -cf out
 """
 
 
@@ -523,7 +525,74 @@ def console_kmer_leiden():
                         help="edges file: every upper-triangle cell, zeros included (the reference), or the kept edges only.")
     parser.add_argument("-kt", "--kmers_top", default=None,
                         help="with --csvfile: also write _kmers_leiden.csv, this many top k-mers (by mean count) per community.")
+    parser.add_argument("-d", "--density", default=None,
+                        help="instead of -pco: keep this fraction of the pairs, the most correlated ones (the cutoff is found on the device).")
     args = _parse_args_or_exit(parser)
+    options = {} if args.density is None else {"density": args.density}
     kmer_leiden.kmer_leiden(args.fasta, args.mean_path, args.std_path, int(args.kmer), args.algo, float(args.rs), float(args.pearsoncutoff),
                             args.setseed, args.edgecolormethod, float(args.edgethreshold), int(args.labelfontsize), args.plotname,
-                            args.csvfile, edges=args.edges, kmers_top=None if args.kmers_top is None else int(args.kmers_top))
+                            args.csvfile, edges=args.edges, kmers_top=None if args.kmers_top is None else int(args.kmers_top), **options)
+
+
+R_DISTRIBUTION_DOC = """
+Description
+-----------
+How the Pearson correlations of the rows of a count file are distributed, on an MI355X and without the all-pairs
+matrix: a histogram, exact quantiles, and the cutoff that keeps a given fraction of the pairs.  One file: the pairs of
+its rows (each once).  Two files: every row of the first against every row of the second.  The histogram goes to a CSV
+file (left,right,count, then the cells below, above and NaN); quantiles and cutoffs are printed as `q,value` lines.
+
+Examples
+--------
+    200 bins over [-1, 1]:                seekr_r_distribution counts.csv --bins 200 --range -1 1 -o hist.csv
+    median and 99th percentile:           seekr_r_distribution counts.npy -bi -q 0.5 0.99
+    the cutoff that keeps 0.1 %% of pairs: seekr_r_distribution counts.npy -bi --density 0.001
+"""
+
+
+def _run_r_distribution(counts, counts2, binary_input, bins, value_range, q, densities, outfile, out=None):
+    import csv
+    from seekr_amd import distribution
+    out = sys.stdout if out is None else out
+    if binary_input:
+        counts = np.load(counts)
+        counts2 = None if counts2 is None else np.load(counts2)
+    else:
+        counts = _read_labelled_csv(counts)[0]
+        counts2 = None if counts2 is None else _read_labelled_csv(counts2)[0]
+    res = distribution.pearson_distribution(counts, counts2, bins=bins, range=value_range, q=q, densities=densities)
+    if res.hist is not None:
+        with open(outfile, "w", newline="") as f:
+            w = csv.writer(f, lineterminator="\n")
+            w.writerow(["left", "right", "count"])
+            for left, right, n in zip(res.edges[:-1], res.edges[1:], res.hist.tolist()):
+                w.writerow([str(left), str(right), n])
+            w.writerow(["-inf", str(res.edges[0]), res.below])
+            w.writerow([str(res.edges[-1]), "inf", res.above])
+            w.writerow(["nan", "nan", res.nan])
+    for x, v in zip(res.q, res.quantiles):
+        out.write("{},{}\n".format(x, str(v)))
+    for d, v in zip(res.densities, res.cutoffs):
+        out.write("density {},{}\n".format(d, str(v)))
+    return res
+
+
+def console_r_distribution():
+    parser = argparse.ArgumentParser(usage=R_DISTRIBUTION_DOC, formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    parser.add_argument("counts", help="Count file whose pairs of rows are looked at.")
+    parser.add_argument("counts2", nargs="?", default=None,
+                        help="Count file whose rows those of `counts` are compared with (default: counts against itself, each pair once).")
+    parser.add_argument("-bi", "--binary_input", action="store_true", help="The count files are .npy, not labelled CSV.")
+    parser.add_argument("--bins", default=None, help="Equal bins of the histogram (with --range; at most 4096).")
+    parser.add_argument("--range", nargs=2, default=None, metavar=("LO", "HI"), help="The histogram's first and last edge.")
+    parser.add_argument("-q", "--quantiles", nargs="+", default=[], help="Quantiles in [0, 1] (decimal or a fraction such as 1/3).")
+    parser.add_argument("--density", nargs="+", default=[], help="Fractions of the pairs whose cutoff is wanted.")
+    parser.add_argument("-o", "--outfile", default="r_histogram.csv", help="Where the histogram goes (CSV: left,right,count).")
+    args = _parse_args_or_exit(parser)
+    if (args.bins is None) != (args.range is None):
+        parser.error("--bins and --range go together")
+    if args.bins is None and not args.quantiles and not args.density:
+        parser.error("nothing asked for: give --bins with --range, -q or --density")
+    _run_r_distribution(args.counts, args.counts2, args.binary_input, None if args.bins is None else int(args.bins),
+                        None if args.range is None else (float(args.range[0]), float(args.range[1])), args.quantiles,
+                        args.density, args.outfile)

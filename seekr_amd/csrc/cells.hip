@@ -16,40 +16,11 @@
 // cells in order within the lane — row-major, no atomic per cell, and the same bytes on every run.
 #include <algorithm>
 
+#include "cell_tile.hpp"
 #include "common.hpp"
 #include "radix.hpp"
 
 namespace {
-
-constexpr int kCellBlock = 256, kCellPer = 4, kCellSegment = kCellBlock * kCellPer;  // 1 024: _lib.SELECT_CELLS_SEGMENT
-
-struct CellArgs {
-    const float* r;
-    int64_t ld, rows, col_begin, col_end, row_global0, col_global0, nseg, tiles;
-    float cutoff;
-};
-
-// the lane's four cells of tile t: v[j] and live[j] (inside the column range); c0 = column of v[0]
-__device__ __forceinline__ void load_group(const CellArgs& a, int64_t t, float (&v)[kCellPer], bool (&live)[kCellPer], int64_t& row,
-                                           int64_t& c0) {
-    row = t / a.nseg;
-    const int64_t seg = t - row * a.nseg;
-    const float* rowp = a.r + (size_t)row * (size_t)a.ld;
-    const int64_t mis = (int64_t)(((uintptr_t)(rowp + a.col_begin) >> 2) & 3);  // cells from the 16-byte boundary below to the first selected cell
-    c0 = a.col_begin - mis + seg * kCellSegment + (int64_t)threadIdx.x * kCellPer;
-    if (c0 >= a.col_begin && c0 + kCellPer <= a.col_end) {
-        const float4 q = *reinterpret_cast<const float4*>(rowp + c0);  // 16-byte aligned by construction
-        v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
-#pragma unroll
-        for (int j = 0; j < kCellPer; j++) live[j] = true;
-    } else {
-#pragma unroll
-        for (int j = 0; j < kCellPer; j++) {
-            live[j] = c0 + j >= a.col_begin && c0 + j < a.col_end;
-            v[j] = live[j] ? rowp[c0 + j] : 0.f;
-        }
-    }
-}
 
 __global__ __launch_bounds__(kCellBlock) void cells_count_pass(CellArgs a, unsigned long long* __restrict__ counts,
                                                                  unsigned* __restrict__ nan_flag) {

@@ -33,6 +33,7 @@ struct SkrKnobs {
     int count_generic_wgs = 0;          // SEEKR_COUNT_GENERIC_WGS=1|2: workgroups per CU of the any-alphabet LDS counter (0: chosen from the shape)
     bool count_k8_global = false;  // SEEKR_COUNT_K8_GLOBAL=1: k = 8 on the round-1 path (histogram in the output row, L2 atomics)
     int count_occ = 0;           // SEEKR_COUNT_OCC: cap on one-wave workgroups per CU of the non-persistent launch (0 = what the LDS allows)
+    int dist_match = 0;          // SEEKR_DIST_MATCH=1: the histogram kernels (distribution.hip) aggregate lanes that hit one bin by two ballot rounds before the LDS atomics; 0 (default) = plain LDS atomics; the same counts
     bool chain_host_wait = false;  // SEEKR_CHAIN_HOST_WAIT=1 (only under SEEKR_TEST_HOOKS=1): the column-sum chain waits for its
                                    // mailbox on the HOST before it launches — several ranks sharing one GPU (tests) cannot wait
                                    // inside a kernel: the waiting kernel fills the CUs and the one it waits for never starts

@@ -95,6 +95,7 @@ extern "C" int skr_ctx_reload_knobs(skr_ctx* c) {
     kn.count_generic_wgs = env_int("SEEKR_COUNT_GENERIC_WGS", 0);
     kn.count_k8_global = env_int("SEEKR_COUNT_K8_GLOBAL", 0) != 0;
     kn.count_occ = std::max(0, env_int("SEEKR_COUNT_OCC", 0));
+    kn.dist_match = env_int("SEEKR_DIST_MATCH", 0) != 0 ? 1 : 0;
     kn.chain_host_wait = env_int("SEEKR_TEST_HOOKS", 0) == 1 && env_int("SEEKR_CHAIN_HOST_WAIT", 0) != 0;
     return SKR_OK;
 }

@@ -80,17 +80,27 @@ def kmer_leiden(inputfile, mean, std, k, algo="RBERVertexPartition", rs=1.0, pea
     """Leiden communities of the sequences of a FASTA file by the Pearson correlation of their k-mer profiles.  Returns
     the membership (int32, one community number per sequence, numbered by size), or None — after the reference's three
     lines — when the mean / std vectors do not fit k.  `csvfile`: writes <csvfile>_nodes_leiden.csv and
-    <csvfile>_edges_leiden.csv (see write_nodes_csv / write_edges_csv for `edges`).  kmers_top=N (the one keyword
+    <csvfile>_edges_leiden.csv (see write_nodes_csv / write_edges_csv for `edges`).  kmers_top=N (a keyword
     `options` takes; default None; with a csvfile): also <csvfile>_kmers_leiden.csv, the kmers_top k-mers with the largest mean count of every community with
-    their mean and sd over its sequences (explain.group_kmers on the counts already on the device)."""
+    their mean and sd over its sequences (explain.group_kmers on the counts already on the device).
+    density=d (the other keyword `options` takes; default None): instead of a pearsoncutoff known in advance, keep the
+    fraction d of the pairs — the cutoff is distribution.density_cutoff on the operand already filled (ties with the
+    cutoff are kept, so at least floor(d N (N - 1) / 2) edges as long as the cutoff is positive); together with a
+    non-zero pearsoncutoff it raises ValueError."""
     if plotname is not None:
         raise NotImplementedError("the network plot is not built here; pass csvfile= and plot the nodes and edges files (plotname={!r})".format(plotname))
     leiden.algo_code(algo)
     kmers_top = options.pop("kmers_top", None)
+    density = options.pop("density", None)
     if options:
         raise TypeError("kmer_leiden() got an unexpected keyword argument {!r}".format(sorted(options)[0]))
     if kmers_top is not None:
         kmers_top = _lib.check_topk_k(kmers_top, "kmers_top")
+    if density is not None:
+        from seekr_amd import distribution
+        if float(pearsoncutoff) != 0:
+            raise ValueError("give density or a non-zero pearsoncutoff, not both (density={!r}, pearsoncutoff={!r})".format(density, pearsoncutoff))
+        distribution.density_rank(density, 1)  # a density lies in (0, 1]
     meanfile = np.load(mean) if isinstance(mean, str) else np.asarray(mean)
     stdfile = np.load(std) if isinstance(std, str) else np.asarray(std)
     if len(meanfile) != 4 ** k or len(stdfile) != 4 ** k:
@@ -105,6 +115,8 @@ def kmer_leiden(inputfile, mean, std, k, algo="RBERVertexPartition", rs=1.0, pea
     x = ctx.from_numpy(np.ascontiguousarray(counter.counts, dtype=np.float32))
     z, _ = _lib.operand_fill(ctx, x, None, pearson_mod._precision_for(np.dtype(np.float32), True))
     try:
+        if density is not None:
+            pearsoncutoff = distribution.density_cutoff(z, density)
         membership, _, info = leiden.pearson_communities(z, float(pearsoncutoff), algo=algo, rs=float(rs))
         groups = None
         if kmers_top is not None and csvfile:

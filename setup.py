@@ -26,6 +26,8 @@ setup(
             "seekr_domain_significant = seekr_amd.console_scripts:console_domain_significant",
             "seekr_kmer_leiden = seekr_amd.console_scripts:console_kmer_leiden",
             "seekr_pair_kmers = seekr_amd.console_scripts:console_pair_kmers",
+            # histogram, exact quantiles and density cutoffs of r, without the all-pairs matrix (no counterpart either)
+            "seekr_r_distribution = seekr_amd.console_scripts:console_r_distribution",
         ]
     },
 )

@@ -2,8 +2,9 @@
 
     python tools/leiden_bench.py [--sparse-rows 100000] [--dense-rows 20000] [--density 1e-3] [--nx-nodes 20000] [--out profiles/leiden_bench.json]
 
-  sparse   --sparse-rows synthetic transcripts of 2 000 bases, k = 6, at the cutoff that keeps about --density of the cells
-           (the 1 - density quantile of a 2 048 x 2 048 block of r)
+  sparse   --sparse-rows synthetic transcripts of 2 000 bases, k = 6, at the cutoff that keeps --density of the pairs
+           (distribution.density_cutoff: exact over all pairs; profiles/leiden_bench.json was made when this was the
+           1 - density quantile of a 2 048 x 2 048 block of r)
   dense    --dense-rows transcripts at cutoff 0, the reference's default, which keeps about half of all cells
 For each: seconds for the edge list (consumers.pearson_edges) and for seekr_amd.leiden.communities, the device time of each
 phase (the library's event timers: sort = CSR build, move, refine, aggregate, number = numbering and the float64 quality),
@@ -19,7 +20,7 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
-from seekr_amd import _lib, consumers, leiden  # noqa: E402
+from seekr_amd import _lib, consumers, distribution, leiden  # noqa: E402
 from seekr_amd import pearson as pearson_mod  # noqa: E402
 from seekr_amd.synthetic import synthetic_ascii  # noqa: E402
 
@@ -36,12 +37,7 @@ def operand(ctx, n, length=2000, k=6):
 
 
 def cutoff_for(ctx, z, density):
-    rows = min(2048, z.rows)
-    buf = ctx.empty(rows, rows)
-    _lib.pearson_gemm_op(ctx, z.view(0, rows), z.view(0, rows), buf)
-    r = buf.to_numpy()
-    buf.free()
-    return float(np.quantile(r[np.triu_indices(rows, 1)], 1.0 - density))
+    return float(distribution.density_cutoff(z, density))
 
 
 def timed_communities(ctx, rows, cols, vals, n, algo="RBERVertexPartition"):
