@@ -472,6 +472,32 @@ int skr_select_cells_ge(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t c
  * allocation: SKR_ERR_INVALID.                                                                                     */
 int skr_vec_copy(skr_ctx* ctx, const skr_mat* src, int64_t src_off, skr_mat* dst, int64_t dst_off, int64_t count);
 
+/* The runs of hot cells inside the tiles of the float32 block r[0:nrows, col_begin:col_end], appended to a list of
+ * PIECES on the device (seekr_amd.windows.domain_hits merges the pieces into hits on the host).  A cell is hot iff
+ * v >= cutoff in float32; NaN is never hot.  The block is cut into skr_select_cells_ge's tiles — one row x one segment of
+ * 1 024 columns, segments starting at a 16-byte boundary of the row's memory, aligned 16-byte loads.  A piece is a maximal
+ * set of hot cells of ONE tile and one sequence in which neighbouring hot cells are separated by at most max_gap cells
+ * that are not hot (max_gap = 0: strictly consecutive; any max_gap >= 0 is accepted).  Nothing is carried between tiles:
+ * a run that crosses a tile edge comes as two pieces, which the caller joins by the same rule (pieces a, b of one row
+ * and one sequence with first_b - last_a - 1 <= max_gap).
+ * seq_of_col: an SKR_U32 device vector indexed by GLOBAL column (col_global0 + j, j = r's own column index) that names
+ * the sequence of every column; a piece never holds columns of two sequences.  Its length must reach col_global0 +
+ * col_end, else SKR_ERR_INVALID.  NULL: every column belongs to one sequence.
+ * Per piece, at cells out_offset ... out_offset + *count - 1 of six vectors: out_rows (SKR_U32, row_global0 + i),
+ * out_first and out_last (SKR_U32, global columns of its first and last hot cell), out_nhot (SKR_U32, its hot cells),
+ * out_peak (SKR_F32, its largest value by the order of skr_hist_key_digits' key: -0 below +0) and out_peak_col (SKR_U32,
+ * the global column of the earliest cell that holds it).  The pieces come in row-major order — by row, then by first
+ * column — and the same input gives the same bytes on every run (integers and maxima only; no global atomic per cell).
+ * *count receives the number of pieces, *saw_nan (may be NULL) whether ANY cell of the range is NaN.  If out_offset +
+ * *count exceeds the capacity of any output nothing is written and the call still returns SKR_OK with the count: the
+ * caller grows its buffers and calls again (skr_select_cells_ge's contract).  With all six NULL only the count and the
+ * flag are made; some but not all NULL: SKR_ERR_INVALID.  Global rows and columns must fit 32 bits.  The block is read
+ * twice: starts per tile, their exclusive scan, then the fill.                                                      */
+int skr_run_pieces_ge(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t col_begin, int64_t col_end,
+                      int64_t row_global0, int64_t col_global0, float cutoff, const skr_mat* seq_of_col, int64_t max_gap,
+                      skr_mat* out_rows, skr_mat* out_first, skr_mat* out_last, skr_mat* out_nhot, skr_mat* out_peak,
+                      skr_mat* out_peak_col, int64_t out_offset, int64_t* count, int* saw_nan);
+
 /* How the cells of the float32 block r[0:nrows, col_begin:col_end] are distributed: counts ADDED into host arrays of
  * uint64_t the caller owns (a run over many blocks accumulates; the device keeps nothing between calls; the calls wait
  * for the device).  Every cell is counted — no zero rule, no diagonal rule; with upper_only != 0 only the cells whose

@@ -15,7 +15,7 @@ LIB = os.path.join(HERE, "libseekr_hip.so")
 DIAG_LIB = os.path.join(HERE, "libseekr_hip_diag.so")
 DIAG_SOURCES = ["pearson_bf16.hip"]  # compiled a second time with -DSEEKR_DIAG for the diagnostic library
 SOURCES = ["ctx.hip", "pack.hip", "count.hip", "windows.hip", "normalize.hip", "normalize_any.hip", "pearson.hip", "pearson_bf16.hip", "operand.hip",
-           "consumers.hip", "cells.hip", "distribution.hip", "topk.hip", "explain.hip", "fused_edges.hip", "adjust.hip", "leiden.hip", "comm.hip", "io.hip", "csv_read.hip", "host_api.hip"]
+           "consumers.hip", "cells.hip", "domain_hits.hip", "distribution.hip", "topk.hip", "explain.hip", "fused_edges.hip", "adjust.hip", "leiden.hip", "comm.hip", "io.hip", "csv_read.hip", "host_api.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-I" + os.path.join(HERE, "..", "include")]
@@ -73,7 +73,10 @@ def build(force=False, verbose=True, diag=False):
         if verbose and proc.stderr.strip():
             print(proc.stderr, file=sys.stderr)
 
-    with ThreadPoolExecutor(max_workers=4) as pool:
+    # the longest compiles first (the contraction, twice with --diag), so that the wall time is theirs and not theirs plus
+    # a queue of short ones; the workers of a pool are mostly waiting for hipcc
+    jobs.sort(key=lambda cmd: -os.path.getsize(cmd[-3]))
+    with ThreadPoolExecutor(max_workers=max(4, min(8, os.cpu_count() or 4))) as pool:
         list(pool.map(run, jobs))
     if len(jobs) > diag_jobs or force or not os.path.exists(LIB):
         run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objs, "-ldl", "-lpthread"])

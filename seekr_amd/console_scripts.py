@@ -4,7 +4,8 @@ counterpart in the reference), `seekr_nearest` (the k most correlated rows of ev
 `seekr_significant_pairs` (the pairs whose corrected p-value is at most alpha, without any N x N matrix: likewise), and
 `seekr_kmer_leiden` with the reference's flags (console_scripts.py:1033-1101) plus --edges, --kmers_top and --density, and
 `seekr_pair_kmers` (the k-mers behind the similarity of listed pairs: no counterpart) and `seekr_r_distribution` (the
-histogram, quantiles and density cutoffs of r without the matrix: likewise).  Only the commands on the hot path are
+histogram, quantiles and density cutoffs of r without the matrix: likewise), and `seekr_domain_significant` and
+`seekr_domain_hits` (the significant windows of a target, and hot windows merged into intervals: likewise).  Only the commands on the hot path are
 provided."""
 import argparse
 import sys
@@ -129,6 +130,25 @@ Examples
 --------
     seekr_domain_significant query.fa target.fa mean.npy std.npy -k 4 -w 500 -s 50 -bg background.npy -o domains.csv
     seekr_domain_significant query.fa target.fa mean.npy std.npy -d norm -p 0.0 0.07 -m bonferroni -a 0.01 -o domains.csv
+"""
+
+DOMAIN_HITS_DOC = """
+Description
+-----------
+The intervals of the target sequences that each query resembles, computed on an MI355X without the query x window
+matrix ever leaving the device: r of every query against every sliding window (as seekr_domain_pearson computes it),
+the windows with r at or above a cutoff, and consecutive such windows of one target sequence merged into hits (at most
+--max_gap windows below the cutoff between two of them).  The cutoff is given (-c), or taken from a background at
+alpha (-bg, or -d with -p: the smallest r whose p-value is at most alpha), or — with -m — the windows are those
+seekr_domain_significant lists.  The output is a CSV with the columns
+query,header,start,end,first_window,last_window,n_windows,n_hot,peak_r,peak_start,peak_end, one line per hit, ordered
+by query and position.
+
+Examples
+--------
+    seekr_domain_hits query.fa target.fa mean.npy std.npy -k 4 -w 500 -s 50 -c 0.2 -g 1 -o hits.csv
+    seekr_domain_hits query.fa target.fa mean.npy std.npy -bg background.npy -a 0.01 -mw 3 -o hits.csv
+    seekr_domain_hits query.fa target.fa mean.npy std.npy -d norm -p 0.0 0.07 -m fdr_bh -o hits.csv
 """
 
 _LOG2 = ["Log2.post", "Log2.pre", "Log2.none"]
@@ -412,6 +432,58 @@ def console_domain_significant():
     _run_domain_significant(args.query, args.target, args.mean, args.std, int(args.kmer), int(args.window), int(args.slide),
                             args.log2, args.outfile, args.background, args.distribution, args.params, args.method,
                             float(args.alpha))
+
+
+HITS_COLUMNS = ["query", "header", "start", "end", "first_window", "last_window", "n_windows", "n_hot", "peak_r", "peak_start",
+                "peak_end"]
+
+
+def _run_domain_hits(query, target, mean, std, kmer, window, slide, log2, outfile, cutoff, background, dist, params, method,
+                     alpha, max_gap, min_windows):
+    import csv
+    from seekr_amd import windows
+    fitres = None if cutoff is not None else _fitres(background, dist, params)
+    frame = windows.domain_hits(query, target, kmer, window, slide, mean, std, cutoff=cutoff, fitres=fitres, alpha=alpha,
+                                method=method, max_gap=max_gap, min_windows=min_windows, log2=log2)
+    with open(outfile, "w", newline="") as f:
+        out = csv.writer(f, lineterminator="\n")
+        out.writerow(HITS_COLUMNS)
+        for row in zip(*(frame[c] for c in HITS_COLUMNS)):
+            out.writerow([str(np.float32(v)) if c == "peak_r" else v if c == "header" else int(v) for c, v in zip(HITS_COLUMNS, row)])
+
+
+def console_domain_hits():
+    parser = argparse.ArgumentParser(usage=DOMAIN_HITS_DOC, formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    parser.add_argument("query", help="FASTA file with the query sequences.")
+    parser.add_argument("target", help="FASTA file with the target sequences; their sliding windows are merged into hits.")
+    parser.add_argument("mean", help="Stored mean vector (.npy) both sides are centred with.")
+    parser.add_argument("std", help="Stored std vector (.npy) both sides are scaled with.")
+    parser.add_argument("-k", "--kmer", default=6, help="k, the word length (4^k columns; up to 7).")
+    parser.add_argument("-w", "--window", default=1000, help="Letters per window.")
+    parser.add_argument("-s", "--slide", default=100, help="Letters between the starts of two windows (at most the window).")
+    parser.add_argument("-l", "--log2", default="Log2.post", choices=_LOG2,
+                        help="log2 before the column statistics (pre), after them (post), or not at all (none).")
+    parser.add_argument("-o", "--outfile", default="domain_hits.csv", help="Where the hits go (CSV: %s)." % ",".join(HITS_COLUMNS))
+    source = parser.add_mutually_exclusive_group(required=True)
+    source.add_argument("-c", "--cutoff", default=None, help="A window is hot when its r is at least this.")
+    source.add_argument("-bg", "--background", default=None,
+                        help="Background similarities: a .npy file or a one-column CSV (find_dist's output without a fit).")
+    source.add_argument("-d", "--distribution", default=None, help="Name of the fitted distribution (with -p).")
+    parser.add_argument("-p", "--params", nargs="+", default=None, help="Its parameters as find_dist lists them (shape, loc, scale).")
+    parser.add_argument("-m", "--method", default=None,
+                        help="Correct the p-values over all queries x windows tests with this method and take the significant "
+                             "windows (default: no correction, the r whose p-value is alpha is the cutoff).")
+    parser.add_argument("-a", "--alpha", default=0.05, help="The p-value (corrected with -m) a window may have at most.")
+    parser.add_argument("-g", "--max_gap", default=0, help="Windows below the cutoff that two windows of one hit may have between them.")
+    parser.add_argument("-mw", "--min_windows", default=1, help="Hits that span fewer windows are dropped.")
+    args = _parse_args_or_exit(parser)
+    if args.distribution is not None and not args.params:
+        parser.error("-d needs the parameters of the distribution: -p P [P ...]")
+    if args.cutoff is not None and args.method is not None:
+        parser.error("-m corrects p-values: it goes with -bg or -d, not with -c")
+    _run_domain_hits(args.query, args.target, args.mean, args.std, int(args.kmer), int(args.window), int(args.slide), args.log2,
+                     args.outfile, None if args.cutoff is None else float(args.cutoff), args.background, args.distribution,
+                     args.params, args.method, float(args.alpha), int(args.max_gap), int(args.min_windows))
 
 
 PAIR_KMERS_DOC = """

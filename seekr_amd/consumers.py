@@ -269,6 +269,42 @@ def select_cells(r, cutoff, into, nrows=None, col_begin=0, col_end=None, row_glo
     return count.value, bool(nan.value)
 
 
+class PieceList(CellList):
+    """CellList's six-vector sibling: the pieces run_pieces leaves on the device — row, first, last, n_hot (uint32), peak
+    (float32) and peak column (uint32).  It grows by the same count-then-write contract."""
+    DTYPES = (np.uint32, np.uint32, np.uint32, np.uint32, np.float32, np.uint32)
+
+    def to_host(self):
+        """The filled part as six host arrays (copies); empty arrays for an empty list."""
+        if not self.n:
+            return tuple(np.empty(0, t) for t in self.DTYPES)
+        return tuple(np.array(m.to_numpy(0, self.n)).reshape(-1) for m in self.bufs)
+
+
+def run_pieces(r, cutoff, into, max_gap=0, seq_of_col=None, nrows=None, col_begin=0, col_end=None, row_global0=0,
+               col_global0=0):
+    """Append the pieces of the device block r[0:nrows, col_begin:col_end] to the PieceList `into`: per tile of one row x
+    1 024 columns the maximal runs of cells with v >= float32(cutoff) (NaN never) of one sequence whose neighbouring hot
+    cells are at most max_gap cold cells apart (skr_run_pieces_ge), in row-major order.  seq_of_col: a uint32 device vector
+    indexed by global column, or None for one sequence.  Returns (count, saw_nan); saw_nan: any cell of the range is NaN.
+    into=None: only the count and the flag are made."""
+    ctx = r.ctx
+    nrows = r.rows if nrows is None else nrows
+    col_end = r.cols if col_end is None else col_end
+    count, nan = C.c_int64(0), C.c_int(0)
+    head = (ctx._h, r._h, int(nrows), int(col_begin), int(col_end), int(row_global0), int(col_global0), C.c_float(cutoff),
+            None if seq_of_col is None else seq_of_col._h, int(max_gap))
+    while True:
+        outs = (None,) * 6 if into is None else tuple(m._h for m in into.bufs)
+        _lib.check(_lib.lib().skr_run_pieces_ge(*head, *outs, 0 if into is None else into.n, C.byref(count), C.byref(nan)))
+        if into is None or into.n + count.value <= into.capacity:
+            break
+        into.reserve(into.n + count.value)  # nothing was written: once more with room
+    if into is not None:
+        into.n += count.value
+    return count.value, bool(nan.value)
+
+
 def pearson_cells(a, b, cutoff, stripe_rows=8192, panel_rows=None):
     """(cells, saw_nan, panelled): the cells of r = a b^T / K with !(r < cutoff) as a CellList (rows index a, columns
     index b), whether one of them is NaN, and whether b was cut into panels.  a, b: prepared operands (_lib.Operand) of

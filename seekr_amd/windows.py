@@ -302,30 +302,33 @@ def domain_significant(query, target, k, window, slide, mean, std, fitres, bestf
     never downloaded; the list is corrected as significant.pearson_significant corrects its candidates and only the
     significant cells cross PCIe.  ValueError: the cutoff is not positive, or r is NaN for a candidate (the first such
     window is named; usually a window of fewer than k letters).  NAN_WARNING as in domain_topk."""
-    from seekr_amd import consumers
     from seekr_amd import significant as sg
     name = sg._check_arguments(fitres, bestfit, method, alpha)
     run = _DomainRun(query, target, k, window, slide, mean, std, log2, chunk_rows, "domain_significant")
+    (q, win, r, p, p_adj), attrs = _significant_cells(run, fitres, bestfit, name, alpha)
+    headers = run.headers()
+    out = _frame({"query": q, "header": headers[run.seq_index[win]] if len(win) else headers[:0], "start": run.start[win],
+                  "end": run.start[win] + run.length[win], "r": r, "p": p, "p_adj": p_adj})
+    out.attrs.update(attrs)
+    return out
+
+
+def _significant_cells(run, fitres, bestfit, name, alpha):
+    """domain_significant's cells: ((query, window, r, p, p_adj) in row-major order, attrs)."""
+    from seekr_amd import consumers
+    from seekr_amd import significant as sg
     ctx, n_tests = run.ctx, run.n_query * run.n_rows
     attrs = {"n_tests": n_tests, "r_cutoff": None, "n_candidates": 0}
-
-    def frame(q, win, r, p, p_adj):
-        headers = run.headers()
-        out = _frame({"query": q, "header": headers[run.seq_index[win]] if len(win) else headers[:0], "start": run.start[win],
-                      "end": run.start[win] + run.length[win], "r": r, "p": p, "p_adj": p_adj})
-        out.attrs.update(attrs)
-        return out
-
     none = np.empty(0, np.int64)
     empty = (none, none, np.empty(0, np.float32), np.empty(0, np.float32), np.empty(0, np.float64))
     if n_tests == 0:
-        return frame(*empty)
+        return empty, attrs
     pv = sg._PValues(ctx, fitres, bestfit)
     held = []
     try:
         r_star = sg.find_cutoff(pv.host, sg.alpha_float32(alpha))
         if r_star is None:
-            return frame(*empty)
+            return empty, attrs
         cutoff = sg.cutoff_with_guard(r_star)
         attrs["r_cutoff"] = cutoff
         cells = consumers.CellList(ctx)
@@ -347,19 +350,144 @@ def domain_significant(query, target, k, window, slide, mean, std, fitres, bestf
                                  w, run.headers()[run.seq_index[w]], run.start[w], run.start[w] + run.length[w]))
         attrs["n_candidates"] = len(cells)
         if len(cells) == 0:
-            return frame(*empty)
+            return empty, attrs
         views = list(cells.prefix())
         held[:0] = views
         out = sg.correct_candidates(pv, *views, n_tests, name, alpha, held)
         if out is None:
-            return frame(*empty)
+            return empty, attrs
         order = sg.row_major_order(out[0], out[1])  # the list came chunk by chunk
         q, win, r, p, p_adj = (a[order] for a in out)
-        return frame(q.astype(np.int64), win.astype(np.int64), r, p, p_adj)
+        return (q.astype(np.int64), win.astype(np.int64), r, p, p_adj), attrs
     finally:
         pv.free()
         for m in held:
             m.free()
+
+
+def _key32(v):
+    """float32 array -> uint32 keys whose order is the order of the values, -0 just below +0 (significant._key)."""
+    u = np.ascontiguousarray(v, dtype=np.float32).view(np.uint32)
+    return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def _unkey32(key):
+    key = np.asarray(key, dtype=np.uint32)
+    return np.where(key & np.uint32(0x80000000), key ^ np.uint32(0x80000000), ~key).astype(np.uint32).view(np.float32)
+
+
+def merge_pieces(row, first, last, n_hot, peak, peak_col, seq_index, max_gap):
+    """The hits of a list of pieces, in any order: (row, first, last, n_hot, peak, peak_col) arrays ordered by (row, first).
+    Two pieces of one row and one sequence (seq_index[first]) are joined iff first_b - last_a - 1 <= max_gap, the pieces
+    taken sorted by (row, first); n_hot adds up, the peak is the larger key (_key32), the earlier window on equal keys.
+    Applied to the pieces of ANY tiling of the cells this gives the hits of the cells, which is why tiles, chunks and
+    launches need no carry.  Vectorised: one lexsort and three reduceat."""
+    row, first, last = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (row, first, last))
+    n_hot, peak_col = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (n_hot, peak_col))
+    peak = np.asarray(peak, dtype=np.float32).reshape(-1)
+    if len(row) == 0:
+        return row, first, last, n_hot, peak, peak_col
+    order = np.lexsort((first, row))
+    row, first, last, n_hot, peak, peak_col = (a[order] for a in (row, first, last, n_hot, peak, peak_col))
+    seq_index = np.asarray(seq_index)
+    join = np.zeros(len(row), dtype=bool)
+    join[1:] = ((row[1:] == row[:-1]) & (seq_index[first[1:]] == seq_index[last[:-1]])
+                & (first[1:] - last[:-1] - 1 <= int(max_gap)))
+    begin = np.flatnonzero(~join)
+    end = np.append(begin[1:], len(row)) - 1
+    # (key << 32) | (0xFFFFFFFF - window): the largest key, then the earliest window
+    packed = (_key32(peak).astype(np.uint64) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - peak_col.astype(np.uint64))
+    best = np.maximum.reduceat(packed, begin)
+    return (row[begin], first[begin], last[end], np.add.reduceat(n_hot, begin), _unkey32((best >> np.uint64(32)).astype(np.uint32)),
+            (np.uint64(0xFFFFFFFF) - (best & np.uint64(0xFFFFFFFF))).astype(np.int64))
+
+
+@_lib.api_call
+def domain_hits(query, target, k, window, slide, mean, std, cutoff=None, fitres=None, bestfit=1, alpha=0.05, method=None,
+                max_gap=0, min_windows=1, log2="Log2.post", chunk_rows=65536):
+    """The intervals of the target each query resembles: hot windows merged into hits.  With r = domain_pearson's matrix
+    for the same arguments, window w is hot for query q iff r[q, w] >= cutoff in float32 (NaN is never hot), and a hit is
+    a maximal set of hot windows of ONE target sequence in which neighbouring hot windows are separated by at most
+    `max_gap` windows that are not hot (0: strictly consecutive).  A DataFrame ordered by (query, first_window) with the
+    columns `query`, `header`, `start`, `end` (first base of the first window, end of the last), `first_window`,
+    `last_window`, `n_windows` (last - first + 1), `n_hot`, `peak_r` (the largest r, -0 below +0), `peak_start`,
+    `peak_end` (the earliest window that reaches it); hits of fewer than `min_windows` windows are dropped.  frame.attrs:
+    r_cutoff, n_pieces, n_hits.  No mean or sum of r: a floating-point sum would depend on how the run is cut.
+
+    Exactly one way of choosing the hot cells:
+      cutoff            a float: hot iff r >= float32(cutoff);
+      fitres, alpha     (method None) cutoff = significant.find_cutoff of the background's p-value at alpha, without a
+                        guard — the smallest float32 r with p <= alpha; it is reported, and None means no hits;
+      fitres, method    the hot cells are domain_significant's cells for the same arguments (its ValueError on NaN stays).
+
+    domain_pearson's loop with one change: each chunk's block of r is cut into pieces on the device (skr_run_pieces_ge:
+    the runs inside one tile of one row x 1 024 windows; nothing is carried between tiles, chunks or launches), r is never
+    downloaded, and after the last chunk only the pieces cross PCIe; merge_pieces joins them across tile and chunk edges.
+    NAN_WARNING as in domain_topk."""
+    from seekr_amd import consumers
+    from seekr_amd import significant as sg
+    if (cutoff is None) == (fitres is None):
+        raise ValueError("give exactly one of `cutoff` and `fitres`")
+    if cutoff is not None and method is not None:
+        raise ValueError("`method` corrects p-values: it needs `fitres`, not `cutoff`")
+    if int(max_gap) != max_gap or max_gap < 0:
+        raise ValueError("max_gap must be a whole number of windows, 0 or more (got {!r})".format(max_gap))
+    if int(min_windows) != min_windows or min_windows < 1:
+        raise ValueError("min_windows must be a whole number, 1 or more (got {!r})".format(min_windows))
+    max_gap, min_windows = int(max_gap), int(min_windows)
+    name = None
+    if cutoff is not None:
+        cutoff = np.float32(cutoff)
+        if np.isnan(cutoff):
+            raise ValueError("cutoff must not be NaN")
+    else:
+        name = sg._check_arguments(fitres, bestfit, "fdr_bh" if method is None else method, alpha)
+    run = _DomainRun(query, target, k, window, slide, mean, std, log2, chunk_rows, "domain_hits")
+    ctx = run.ctx
+    attrs = {"r_cutoff": None if cutoff is None else float(cutoff), "n_pieces": 0, "n_hits": 0}
+    none = np.empty(0, np.int64)
+    pieces = (none, none, none, none, np.empty(0, np.float32), none)
+    if run.n_query * run.n_rows == 0:
+        pass
+    elif method is not None:
+        (q, win, r, _, _), cell_attrs = _significant_cells(run, fitres, bestfit, name, alpha)
+        attrs["r_cutoff"] = None if cell_attrs["r_cutoff"] is None else float(cell_attrs["r_cutoff"])
+        pieces = (q, win, win, np.ones(len(q), np.int64), r, win)
+    else:
+        if cutoff is None:
+            pv = sg._PValues(ctx, fitres, bestfit)
+            try:
+                cutoff = sg.find_cutoff(pv.host, sg.alpha_float32(alpha))
+            finally:
+                pv.free()
+            attrs["r_cutoff"] = None if cutoff is None else float(cutoff)
+        if cutoff is not None:
+            seq_of_col = ctx.from_numpy(run.seq_index.astype(np.uint32))  # once per call
+            found = consumers.PieceList(ctx)
+            try:
+                nan_seen = False
+                for r0, n, r_dev, has_nan in run.blocks():
+                    _, saw = consumers.run_pieces(r_dev, float(cutoff), found, max_gap=max_gap, seq_of_col=seq_of_col,
+                                                  nrows=run.n_query, col_begin=0, col_end=n, row_global0=0, col_global0=r0)
+                    nan_seen = nan_seen or has_nan or saw
+                if nan_seen:
+                    print(NAN_WARNING)
+                pieces = found.to_host()
+            finally:
+                found.free()
+                seq_of_col.free()
+    attrs["n_pieces"] = len(pieces[0])
+    q, first, last, n_hot, peak, peak_win = merge_pieces(*pieces, run.seq_index, max_gap)
+    keep = last - first + 1 >= min_windows
+    q, first, last, n_hot, peak, peak_win = (a[keep] for a in (q, first, last, n_hot, peak, peak_win))
+    attrs["n_hits"] = len(q)
+    headers = run.headers()
+    out = _frame({"query": q, "header": headers[run.seq_index[first]] if len(q) else headers[:0], "start": run.start[first],
+                  "end": run.start[last] + run.length[last], "first_window": first, "last_window": last,
+                  "n_windows": last - first + 1, "n_hot": n_hot, "peak_r": peak, "peak_start": run.start[peak_win],
+                  "peak_end": run.start[peak_win] + run.length[peak_win]})
+    out.attrs.update(attrs)
+    return out
 
 
 def window_labels(table):

@@ -24,6 +24,8 @@ setup(
             "seekr_significant_pairs = seekr_amd.console_scripts:console_significant_pairs",
             # the windows of a target each query is significantly similar to (no counterpart either)
             "seekr_domain_significant = seekr_amd.console_scripts:console_domain_significant",
+            # hot windows of a target merged into intervals per query (no counterpart either)
+            "seekr_domain_hits = seekr_amd.console_scripts:console_domain_hits",
             "seekr_kmer_leiden = seekr_amd.console_scripts:console_kmer_leiden",
             "seekr_pair_kmers = seekr_amd.console_scripts:console_pair_kmers",
             # histogram, exact quantiles and density cutoffs of r, without the all-pairs matrix (no counterpart either)
