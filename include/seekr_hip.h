@@ -366,7 +366,8 @@ int skr_pearson_gemm_op(skr_ctx* ctx, const skr_operand* a, const skr_operand* b
 int skr_pearson_gemm_op_rows(skr_ctx* ctx, const skr_operand* a, const skr_operand* full, int64_t a_row0, skr_mat* r,
                              int64_t row0);
 /* The float64 contraction of skr_pearson as a step of its own: r[row0 + i, col0 + j] = <a_i, b_j> / K for float64 rows
- * that are standardised already (skr_row_standardize) and may be zero-padded to a->cols >= K columns.  symmetric != 0:
+ * that are standardised already (skr_row_standardize) and may be wider than K (a->cols >= K: zero-padded, say — only the
+ * first K columns enter the sum).  symmetric != 0:
  * a and b are the same rows (one triangle computed and mirrored).  Float64 products round once, so stripes of a
  * self-comparison need no swapped form: any tiling gives the same bits.                                             */
 int skr_pearson_gemm_f64(skr_ctx* ctx, const skr_mat* a, const skr_mat* b, int64_t K, int symmetric, skr_mat* r,

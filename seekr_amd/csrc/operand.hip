@@ -2024,7 +2024,8 @@ extern "C" int skr_pearson_gemm(skr_ctx* ctx, const skr_mat* a, const skr_mat* b
 /* r[row0 + i, col0 + j] = <a_i, b_j> / K for float64 rows that are standardised already and may be zero-padded (the
  * stored width a->cols >= K; skr_pearson pads to whole 16-column stages): the contraction of skr_pearson's float64 path
  * as a step of its own, for callers that produce r one row stripe at a time or hold the rows of b on several GPUs.
- * A product of two doubles has one rounding, so a_i . b_j and b_j . a_i are the same bits: stripes need no swapped form. */
+ * A product of two doubles has one rounding, so a_i . b_j and b_j . a_i are the same bits: stripes need no swapped form.
+ * Only the first K columns enter the sum: what wider rows hold beyond them need not be zero. */
 extern "C" int skr_pearson_gemm_f64(skr_ctx* ctx, const skr_mat* a, const skr_mat* b, int64_t K, int symmetric, skr_mat* r,
                                     int64_t row0, int64_t col0) {
     SKR_TRY(check_pair(ctx, a, b));
@@ -2038,7 +2039,7 @@ extern "C" int skr_pearson_gemm_f64(skr_ctx* ctx, const skr_mat* a, const skr_ma
     if (a->rows == 0 || b->rows == 0) return SKR_OK;
     return skr_launch_gemm_f64(ctx, (const double*)a->data, (const double*)b->data,
                                (double*)r->data + (size_t)row0 * r->cols + col0, a->rows, b->rows, a->cols, a->cols, b->cols,
-                               r->cols, (double)K, symmetric && a->data == b->data && a->rows == b->rows);
+                               r->cols, (double)K, symmetric && a->data == b->data && a->rows == b->rows, K);
 }
 
 extern "C" int skr_pearson(skr_ctx* ctx, const skr_mat* counts1, const skr_mat* counts2, int row_standardize,

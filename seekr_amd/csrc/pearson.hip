@@ -314,6 +314,11 @@ template <bool SYM>
 __global__ __launch_bounds__(256, 2) void pearson_gemm_f64_tiled_kernel(
     const double* __restrict__ A, const double* __restrict__ B, double* __restrict__ C, int64_t M, int64_t N, int64_t K,
     int64_t lda, int64_t ldb, int64_t ldc, double kdiv, int64_t tiles_n) {
+    // Kv: the columns that count; the loop runs over the whole stages that cover them (the launcher has made sure the
+    // rows are that wide) — what the last stage holds beyond Kv is read and replaced by zeros (the caller's rows may be
+    // wider than the K it asked for, and need not be zero there)
+    const int64_t Kv = K;
+    K = (Kv + DK - 1) / DK * DK;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int64_t tm = blockIdx.x / tiles_n, tn = blockIdx.x % tiles_n;
     if (SYM && tn < tm) return;
@@ -368,6 +373,10 @@ __global__ __launch_bounds__(256, 2) void pearson_gemm_f64_tiled_kernel(
                 const int pos = ((kk * 2 + (kq >> 1)) ^ (r16 >> 1)) << 4;
                 a[t] = *reinterpret_cast<const double*>(abase + t * 16 * kRowBytes64 + pos);
                 b[t] = *reinterpret_cast<const double*>(bbase + t * 16 * kRowBytes64 + pos);
+            }
+            if (k0 + DK > Kv && k0 + kk * 4 + kq >= Kv) {  // the last stage only: this lane's column kk * 4 + kq is past Kv
+#pragma unroll
+                for (int t = 0; t < 4; t++) a[t] = b[t] = 0.0;
             }
 #pragma unroll
             for (int i = 0; i < 4; i++)
@@ -435,24 +444,27 @@ int skr_launch_gemm_f32(skr_ctx* ctx, const float* A, const float* B, float* C, 
 }
 
 int skr_launch_gemm_f64(skr_ctx* ctx, const double* A, const double* B, double* C, int64_t M, int64_t N, int64_t K,
-                        int64_t lda, int64_t ldb, int64_t ldc, double kdiv, int symmetric) {
+                        int64_t lda, int64_t ldb, int64_t ldc, double kdiv, int symmetric, int64_t Kvalid) {
+    // K: the columns a row holds; Kvalid (< 0: all of them): the columns that enter the sum
     SkrProfScope prof(ctx, "pearson_gemm_f64");
-    if (K % DK == 0 && lda % 2 == 0 && ldb % 2 == 0) {  // whole stages, 16-byte aligned rows: the tiled kernel
+    const int64_t Kv = Kvalid < 0 ? K : std::min(K, Kvalid);
+    const int64_t Kst = (Kv + DK - 1) / DK * DK;
+    if (Kst <= K && lda % 2 == 0 && ldb % 2 == 0) {  // whole stages inside the rows, 16-byte aligned rows: the tiled kernel
         const int64_t tiles_m = (M + DT - 1) / DT, tiles_n = (N + DT - 1) / DT;
         const bool sym = symmetric && A == B && M == N && lda == ldb;  // mirrors land inside the same square block
         if (sym) {
             SKR_TRY(skr_kernel_lds(ctx, reinterpret_cast<const void*>(pearson_gemm_f64_tiled_kernel<true>), 2 * kStageBytes64));
             hipLaunchKernelGGL(pearson_gemm_f64_tiled_kernel<true>, dim3((unsigned)(tiles_m * tiles_n)), dim3(256),
-                               2 * kStageBytes64, ctx->stream, A, B, C, M, N, K, lda, ldb, ldc, kdiv, tiles_n);
+                               2 * kStageBytes64, ctx->stream, A, B, C, M, N, Kv, lda, ldb, ldc, kdiv, tiles_n);
         } else {
             SKR_TRY(skr_kernel_lds(ctx, reinterpret_cast<const void*>(pearson_gemm_f64_tiled_kernel<false>), 2 * kStageBytes64));
             hipLaunchKernelGGL(pearson_gemm_f64_tiled_kernel<false>, dim3((unsigned)(tiles_m * tiles_n)), dim3(256),
-                               2 * kStageBytes64, ctx->stream, A, B, C, M, N, K, lda, ldb, ldc, kdiv, tiles_n);
+                               2 * kStageBytes64, ctx->stream, A, B, C, M, N, Kv, lda, ldb, ldc, kdiv, tiles_n);
         }
     } else {
         const int64_t tiles_m = (M + 31) / 32, tiles_n = (N + 31) / 32;
         const unsigned grid = (unsigned)((tiles_m * tiles_n + 3) / 4);
-        hipLaunchKernelGGL(pearson_gemm_f64_kernel, dim3(grid), dim3(256), 0, ctx->stream, A, B, C, M, N, K, lda, ldb, ldc,
+        hipLaunchKernelGGL(pearson_gemm_f64_kernel, dim3(grid), dim3(256), 0, ctx->stream, A, B, C, M, N, Kv, lda, ldb, ldc,
                            kdiv, tiles_n);
     }
     SKR_HIP(hipGetLastError());

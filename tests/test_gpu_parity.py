@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from oracle import seekr_oracle as orc
+from exact_sum_cases import f16_halves
 from inputs import EXAMPLE_FA, big_count_matrix, skewed_set, synth_2000, write_fasta
 
 pytestmark = pytest.mark.gpu
@@ -674,16 +675,7 @@ def test_split_halves_against_a_numpy_restatement(cols, L, ctx):
     assert op.kind == 2
     kt = (cols + 31) // 32
     got = op.as_matrix().to_numpy().view(np.uint16).reshape(rows, kt, 2, 32)
-    zs = x * scale
-    col = np.arange(cols, dtype=np.uint64)
-    up = (((col * np.uint64(0x9E3779B1)) & np.uint64(0xFFFFFFFF)) >> np.uint64(31)).astype(bool)[None, :]
-    with np.errstate(all="ignore"):
-        h = zs.astype(np.float16)
-        back = h.astype(np.float32)
-        h_up = np.where(back < zs, np.nextafter(h, np.float16(np.inf)), h)
-        h_dn = np.where(back > zs, np.nextafter(h, np.float16(-np.inf)), h)
-        hi = np.where(up, h_up, h_dn).astype(np.float16)
-        lo = (zs - hi.astype(np.float32)).astype(np.float16)
+    hi, lo, up = f16_halves(x, scale)  # the numpy restatement (tests/exact_sum_cases.py, shared with the exact-sum tests)
     pad = np.zeros((rows, kt * 32 - cols), np.uint16)  # +0
     want_hi = np.concatenate([hi.view(np.uint16), pad], axis=1).reshape(rows, kt, 32)
     want_lo = np.concatenate([lo.view(np.uint16), pad], axis=1).reshape(rows, kt, 32)
