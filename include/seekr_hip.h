@@ -87,6 +87,8 @@ int skr_ctx_sync(skr_ctx* ctx);
 /* Free and total device memory of the ctx's GPU in bytes (hipMemGetInfo): callers size stripes and tests against it. */
 int skr_ctx_mem_info(skr_ctx* ctx, uint64_t* free_bytes, uint64_t* total_bytes);
 int skr_ctx_device(const skr_ctx* ctx, int* device);
+/* compute units of the ctx's device (what the persistent launches size their grids by) */
+int skr_ctx_compute_units(const skr_ctx* ctx, int* count);
 /* The SEEKR_GEMM_* / SEEKR_COUNT_* A/B switches are read from the environment when the ctx is created;
  * this reads them again (bench tools that interleave variants in one process).  No launch calls getenv.            */
 int skr_ctx_reload_knobs(skr_ctx* ctx);

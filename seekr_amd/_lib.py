@@ -39,6 +39,7 @@ SIGNATURES = {
     "skr_ctx_sync": (_int, [_p]),
     "skr_ctx_mem_info": (_int, [_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "skr_ctx_device": (_int, [_p, C.POINTER(_int)]),
+    "skr_ctx_compute_units": (_int, [_p, C.POINTER(_int)]),
     "skr_ctx_reload_knobs": (_int, [_p]),
     "skr_prof_enable": (_int, [_p, _int]),
     "skr_prof_reset": (_int, [_p]),
@@ -325,6 +326,12 @@ class Context:
         f, t = C.c_uint64(0), C.c_uint64(0)
         check(lib().skr_ctx_mem_info(self._h, C.byref(f), C.byref(t)))
         return f.value, t.value
+
+    def compute_units(self):
+        """Compute units of the device (skr_ctx_compute_units): what the persistent launches size their grids by."""
+        n = _int(0)
+        check(lib().skr_ctx_compute_units(self._h, C.byref(n)))
+        return n.value
 
     def reload_knobs(self):
         """Re-read the SEEKR_GEMM_* / SEEKR_COUNT_* A/B switches from os.environ (they are otherwise read once, at creation)."""

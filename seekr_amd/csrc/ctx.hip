@@ -260,6 +260,12 @@ extern "C" int skr_ctx_device(const skr_ctx* ctx, int* device) {
     return SKR_OK;
 }
 
+extern "C" int skr_ctx_compute_units(const skr_ctx* ctx, int* count) {
+    SKR_REQUIRE(ctx && count, "NULL argument");
+    *count = ctx->num_cu;
+    return SKR_OK;
+}
+
 int skr_kernel_lds(skr_ctx* ctx, const void* kern, size_t bytes) {
     auto it = ctx->lds_attr.find(kern);
     if (it != ctx->lds_attr.end() && (size_t)it->second >= bytes) return SKR_OK;
