@@ -1159,14 +1159,21 @@ def check_topk_k(k, what="k"):
     return int(k)
 
 
+def block_args(r, nrows=None, col_begin=0, col_end=None, row_global0=0, col_global0=0):
+    """(ctx, r, nrows, col_begin, col_end, row_global0, col_global0): the leading arguments of every library call that
+    reads the block r[0:nrows, col_begin:col_end] of a device matrix whose cell (0, 0) is cell (row_global0, col_global0)
+    of the whole r.  nrows / col_end None: all rows / up to the last column."""
+    return (r.ctx._h, r._h, int(r.rows if nrows is None else nrows), int(col_begin),
+            int(r.cols if col_end is None else col_end), int(row_global0), int(col_global0))
+
+
 def topk_merge_rows(ctx, r, idx, val, k, first, nrows=None, col_begin=0, col_end=None, row_global0=0, col_global0=0,
                     exclude_diag=True, want_nan=False):
     """skr_topk_merge_rows: the k best of (the lists in idx / val, unless `first`) and the cells r[0:nrows,
     col_begin:col_end] into idx / val (uint32 / float32 device matrices of at least nrows * k cells).  Returns saw_nan
     (False without want_nan: the call then does not wait for the device)."""
     nan = _int(0)
-    check(lib().skr_topk_merge_rows(ctx._h, r._h, int(r.rows if nrows is None else nrows), int(col_begin),
-                                    int(r.cols if col_end is None else col_end), int(row_global0), int(col_global0),
+    check(lib().skr_topk_merge_rows(*block_args(r, nrows, col_begin, col_end, row_global0, col_global0),
                                     1 if exclude_diag else 0, int(k), 1 if first else 0, idx._h, val._h,
                                     C.byref(nan) if want_nan else None))
     return bool(nan.value)

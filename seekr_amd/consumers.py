@@ -7,8 +7,12 @@ it: keeping these reductions on the GPU avoids shipping an N x N m
     empirical_pvalues     find_pval.py:158-164   p[i,j] = np.sum(fitres > sim[i,j]) / len(fitres)
     edges / pearson_edges kmer_leiden.py:91-96   the thresholded matrix as an edge list, r produced and consumed
                                                  one row stripe at a time (N x N never exists)
-    topk_rows / pearson_topk  —                  the k most correlated rows of every row; pearson_topk merges r block by
-                                                 block into running lists (N x N never exists)
+    Sweep                 —                      r one [stripe, panel] block after another in one reusable buffer, each handed
+                                                 to a visitor (N x N never exists): all of a x b, or the upper triangle of
+                                                 a x a.  Its visitors: pearson_cells, pearson_topk, seekr_amd.distribution
+    select_cells / pearson_cells  —              the cells with !(r < cutoff) as a device list; pearson_cells over a Sweep
+    topk_rows / pearson_topk  —                  the k most correlated rows of every row; pearson_topk merges a Sweep's
+                                                 blocks into running lists
     adjust_pvalues        adj_pval.py:53-138     multipletests on the p-value matrix (symmetric: upper triangle)
     adjust_pvalues_head   —                      the same for the smallest p-values of a longer list (seekr_amd.significant)
     select_le / gather_index  —                  the positions of a vector with value <= bound, and a gather by them
@@ -16,12 +20,14 @@ it: keeping these reductions on the GPU avoids shipping an N x N m
 Every function takes and returns device matrices (`seekr_amd._lib.Matrix`); `*_host` helpers
 wrap host arrays for drop-in use.
 """
+import contextlib
 import ctypes as C
 import os
 
 import numpy as np
 
 from seekr_amd import _lib
+from seekr_amd._lib import block_args  # the head of every call on a block of r
 
 
 def threshold_zero_diag(r, cutoff, diag_col0=0):
@@ -60,6 +66,19 @@ def ceil_float32(values):
     with np.errstate(over="ignore", invalid="ignore"):
         near = wide.astype(np.float32)  # beyond float32's range: +-inf, and -inf steps up to -FLT_MAX below
         return np.where(near < wide, np.nextafter(near, np.float32(np.inf)), near).astype(np.float32)
+
+
+def float32_key(v):
+    """float32 array -> uint32 keys whose order is the order of the values, -0 just below +0 (NaN: above +inf with the
+    sign bit clear, below -inf with it set)."""
+    u = np.ascontiguousarray(v, dtype=np.float32).view(np.uint32)
+    return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def float32_unkey(key):
+    """uint32 keys -> the float32 array they are the keys of, bit for bit."""
+    key = np.asarray(key, dtype=np.uint32)
+    return np.where(key & np.uint32(0x80000000), key ^ np.uint32(0x80000000), ~key).astype(np.uint32).view(np.float32)
 
 
 def empirical_pvalues(r, fitres):
@@ -113,11 +132,8 @@ def edges(r, cutoff, nrows=None, col_begin=0, col_end=None, row_global0=0, col_g
     r[0:nrows, col_begin:col_end] that kmer_leiden.py:94-96 leaves non-zero, in np.nonzero order.  into: a CellList the
     outputs are appended to on the device instead; the number of edges is returned."""
     ctx = r.ctx
-    nrows = r.rows if nrows is None else nrows
-    col_end = r.cols if col_end is None else col_end
     count = C.c_int64(0)
-    args = (ctx._h, r._h, int(nrows), int(col_begin), int(col_end), int(row_global0), int(col_global0),
-            C.c_float(cutoff), 1 if upper_only else 0)
+    args = (*block_args(r, nrows, col_begin, col_end, row_global0, col_global0), C.c_float(cutoff), 1 if upper_only else 0)
     _lib.check(_lib.lib().skr_edges(*args, None, None, None, C.byref(count)))
     n = count.value
     if n == 0:
@@ -248,25 +264,29 @@ class CellList:
         self.bufs, self.n, self.capacity = (), 0, 0
 
 
-def select_cells(r, cutoff, into, nrows=None, col_begin=0, col_end=None, row_global0=0, col_global0=0):
-    """Append the cells of the device block r[0:nrows, col_begin:col_end] with !(v < cutoff) to the CellList `into`, as
-    (row_global0 + i, col_global0 + j, v) in np.nonzero order of the mask: NaN and cells equal to the cutoff are kept,
-    zeros and the diagonal are cells like any other (skr_select_cells_ge).  Returns (count, saw_nan).  into=None: only
-    the count and the flag are made."""
-    ctx = r.ctx
-    nrows = r.rows if nrows is None else nrows
-    col_end = r.cols if col_end is None else col_end
+def _count_then_write(into, width, call):
+    """(count, saw_nan) of one block appended to the CellList `into` (None: counted only, `width` NULL outputs).
+    call(*outputs, offset, count, nan) is the library call: it writes behind `offset` when the block fits into the
+    outputs and only counts when it does not; the list then grows and the call is made once more."""
     count, nan = C.c_int64(0), C.c_int(0)
-    head = (ctx._h, r._h, int(nrows), int(col_begin), int(col_end), int(row_global0), int(col_global0), C.c_float(cutoff))
     while True:
-        outs = (None, None, None) if into is None else tuple(m._h for m in into.bufs)
-        _lib.check(_lib.lib().skr_select_cells_ge(*head, *outs, 0 if into is None else into.n, C.byref(count), C.byref(nan)))
+        outs = (None,) * width if into is None else tuple(m._h for m in into.bufs)
+        _lib.check(call(*outs, 0 if into is None else into.n, C.byref(count), C.byref(nan)))
         if into is None or into.n + count.value <= into.capacity:
             break
         into.reserve(into.n + count.value)  # nothing was written: once more with room
     if into is not None:
         into.n += count.value
     return count.value, bool(nan.value)
+
+
+def select_cells(r, cutoff, into, nrows=None, col_begin=0, col_end=None, row_global0=0, col_global0=0):
+    """Append the cells of the device block r[0:nrows, col_begin:col_end] with !(v < cutoff) to the CellList `into`, as
+    (row_global0 + i, col_global0 + j, v) in np.nonzero order of the mask: NaN and cells equal to the cutoff are kept,
+    zeros and the diagonal are cells like any other (skr_select_cells_ge).  Returns (count, saw_nan).  into=None: only
+    the count and the flag are made."""
+    head = (*block_args(r, nrows, col_begin, col_end, row_global0, col_global0), C.c_float(cutoff))
+    return _count_then_write(into, 3, lambda *tail: _lib.lib().skr_select_cells_ge(*head, *tail))
 
 
 class PieceList(CellList):
@@ -288,70 +308,98 @@ def run_pieces(r, cutoff, into, max_gap=0, seq_of_col=None, nrows=None, col_begi
     cells are at most max_gap cold cells apart (skr_run_pieces_ge), in row-major order.  seq_of_col: a uint32 device vector
     indexed by global column, or None for one sequence.  Returns (count, saw_nan); saw_nan: any cell of the range is NaN.
     into=None: only the count and the flag are made."""
-    ctx = r.ctx
-    nrows = r.rows if nrows is None else nrows
-    col_end = r.cols if col_end is None else col_end
-    count, nan = C.c_int64(0), C.c_int(0)
-    head = (ctx._h, r._h, int(nrows), int(col_begin), int(col_end), int(row_global0), int(col_global0), C.c_float(cutoff),
+    head = (*block_args(r, nrows, col_begin, col_end, row_global0, col_global0), C.c_float(cutoff),
             None if seq_of_col is None else seq_of_col._h, int(max_gap))
-    while True:
-        outs = (None,) * 6 if into is None else tuple(m._h for m in into.bufs)
-        _lib.check(_lib.lib().skr_run_pieces_ge(*head, *outs, 0 if into is None else into.n, C.byref(count), C.byref(nan)))
-        if into is None or into.n + count.value <= into.capacity:
-            break
-        into.reserve(into.n + count.value)  # nothing was written: once more with room
-    if into is not None:
-        into.n += count.value
-    return count.value, bool(nan.value)
+    return _count_then_write(into, 6, lambda *tail: _lib.lib().skr_run_pieces_ge(*head, *tail))
+
+
+class Sweep:
+    """The blocks of r = a b^T / K for prepared operands (_lib.Operand), one after another in one reusable
+    [stripe_rows, panel_rows] buffer: per stripe of `stripe_rows` rows of a (clamped to 1 ... a.rows), per panel of
+    `panel_rows` rows of b (None: all of b), skr_pearson_gemm_op and then the visitor, before the next contraction
+    overwrites the block.  b=None: the upper triangle of a against itself — a stripe's panels start at its first row
+    and the visitor is told upper_only=True; else all of a x b.  This is the only producer of [stripe, panel] blocks;
+    pearson_cells, pearson_topk and seekr_amd.distribution are visitors.
+
+    The buffer is allocated by the first run() that has a block to make and kept for the next one (an order statistic
+    sweeps several times) until free(); `with Sweep(...) as sweep:` frees it.  A block that is a whole operand is
+    contracted from the operand itself; every other block from views that are freed when the block is done, also when
+    the contraction or the visitor raises."""
+
+    def __init__(self, a, b=None, stripe_rows=8192, panel_rows=None):
+        self.a, self.b, self.upper_only = a, (a if b is None else b), b is None
+        n, m = a.rows, self.b.rows
+        self.stripe_rows = max(1, min(int(stripe_rows), max(n, 1)))
+        self.panel_rows = max(m, 1) if panel_rows is None else max(1, min(int(panel_rows), max(m, 1)))
+        self.buf = None
+
+    def run(self, visit):
+        """visit(buf, nrows=, col_begin=, col_end=, row_global0=, col_global0=, upper_only=) for every block, stripes
+        outermost.  The first panel of a stripe has col_global0 == 0 in a sweep of all of a x b, and the last one ends at
+        col_global0 + col_end - col_begin == b.rows.  Nothing is allocated or called when a or b has no rows."""
+        a, b = self.a, self.b
+        n, m = a.rows, b.rows
+        if n == 0 or m == 0:
+            return
+        if self.buf is None:
+            self.buf = a.ctx.empty(self.stripe_rows, self.panel_rows)
+        for s0 in range(0, n, self.stripe_rows):
+            rows = min(self.stripe_rows, n - s0)
+            a_s = a if rows == n else a.view(s0, rows)
+            try:
+                for p0 in range(s0 if self.upper_only else 0, m, self.panel_rows):
+                    cols = min(self.panel_rows, m - p0)
+                    b_p = b if cols == m else b.view(p0, cols)
+                    try:
+                        _lib.pearson_gemm_op(a.ctx, a_s, b_p, self.buf)
+                        visit(self.buf, nrows=rows, col_begin=0, col_end=cols, row_global0=s0, col_global0=p0,
+                              upper_only=self.upper_only)
+                    finally:
+                        if b_p is not b:
+                            b_p.free()
+            finally:
+                if a_s is not a:
+                    a_s.free()
+
+    def free(self):
+        if self.buf is not None:
+            self.buf.free()
+            self.buf = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
 
 
 def pearson_cells(a, b, cutoff, stripe_rows=8192, panel_rows=None):
     """(cells, saw_nan, panelled): the cells of r = a b^T / K with !(r < cutoff) as a CellList (rows index a, columns
     index b), whether one of them is NaN, and whether b was cut into panels.  a, b: prepared operands (_lib.Operand) of
-    one storage kind, as neighbors._prepare leaves them.  Per stripe of `stripe_rows` rows of a and per panel of
-    `panel_rows` rows of b (None: all of b): skr_pearson_gemm_op into one reusable [stripe_rows, panel_rows] buffer, then
-    select_cells — pearson_topk's loop.  Without panels the list is row-major; with them it is row-major within each
-    (stripe, panel) block, the blocks in loop order.  The caller frees the list."""
-    ctx = a.ctx
+    one storage kind, as neighbors._prepare leaves them.  Every block of Sweep(a, b, stripe_rows, panel_rows) goes through
+    select_cells.  Without panels the list is row-major; with them it is row-major within each (stripe, panel) block, the
+    blocks in the sweep's order.  The caller frees the list."""
     n, m = a.rows, b.rows
-    cells = CellList(ctx, max(1 << 16, min(int(2e-3 * n * m), 1 << 26)))
+    cells = CellList(a.ctx, max(1 << 16, min(int(2e-3 * n * m), 1 << 26)))
     if n == 0 or m == 0:
         return cells, False, False
-    stripe_rows = max(1, min(int(stripe_rows), n))
-    panel_rows = m if panel_rows is None else max(1, min(int(panel_rows), m))
-    buf = ctx.empty(stripe_rows, panel_rows)
-    saw_nan = False
+    nans = []
     try:
-        for s0 in range(0, n, stripe_rows):
-            rows = min(stripe_rows, n - s0)
-            a_s = a if rows == n else a.view(s0, rows)
-            for p0 in range(0, m, panel_rows):
-                cols = min(panel_rows, m - p0)
-                b_p = b if cols == m else b.view(p0, cols)
-                _lib.pearson_gemm_op(ctx, a_s, b_p, buf)
-                _, nan = select_cells(buf, cutoff, cells, nrows=rows, col_begin=0, col_end=cols, row_global0=s0, col_global0=p0)
-                saw_nan = saw_nan or nan
-                if b_p is not b:
-                    b_p.free()
-            if a_s is not a:
-                a_s.free()
+        with Sweep(a, b, stripe_rows, panel_rows) as sweep:
+            sweep.run(lambda buf, upper_only, **where: nans.append(select_cells(buf, cutoff, cells, **where)[1]))
     except BaseException:
         cells.free()
         raise
-    finally:
-        buf.free()
-    return cells, saw_nan, panel_rows < m
+    return cells, any(nans), sweep.panel_rows < m
 
 
 def topk_rows(r, k, nrows=None, col_begin=0, col_end=None, row_global0=0, col_global0=0):
     """(idx uint32 [nrows, k], val float32 [nrows, k]): the k largest cells of each row of the device
     block, descending, diagonal cell excluded — np.argsort(-row, kind="stable")[:k] per row."""
-    ctx = r.ctx
-    nrows = r.rows if nrows is None else nrows
-    col_end = r.cols if col_end is None else col_end
-    idx, val = ctx.empty(nrows, k, np.uint32), ctx.empty(nrows, k, np.float32)
-    _lib.check(_lib.lib().skr_topk_rows(ctx._h, r._h, int(nrows), int(col_begin), int(col_end), int(row_global0),
-                                        int(col_global0), int(k), idx._h, val._h))
+    head = block_args(r, nrows, col_begin, col_end, row_global0, col_global0)
+    nrows = head[2]
+    idx, val = r.ctx.empty(nrows, k, np.uint32), r.ctx.empty(nrows, k, np.float32)
+    _lib.check(_lib.lib().skr_topk_rows(*head, int(k), idx._h, val._h))
     out = idx.to_numpy(), val.to_numpy()
     idx.free()
     val.free()
@@ -364,13 +412,13 @@ def pearson_topk(a, b=None, k=10, stripe_rows=8192, panel_rows=None):
     NaN last and ties to the smaller row of b; rows with fewer than k candidates are padded with 0xFFFFFFFF / NaN.
     b=None: `a` against itself, a row's own cell excluded.
 
-    r never stands whole: per stripe of `stripe_rows` rows of a, each panel of `panel_rows` rows of b (None: all of b) is
-    contracted into one reusable [stripe_rows, panel_rows] buffer and merged into the stripe's running lists
-    (skr_topk_merge_rows: one read of the buffer, whatever k is); only the finished [stripe, k] lists cross PCIe.
-    Device memory is stripe_rows x panel_rows floats plus the lists.  The order is total, so the result does not depend
-    on either split.  Operands of either kind (split halves or float32 layout) run the same two steps, as pearson_edges'
-    two-step path does.  Not done here: the self-comparison contracts every block, not half of them (r's symmetry is
-    not used), and the selection is a pass of its own over the buffer, not part of the contraction's epilogue."""
+    r never stands whole: every block of Sweep(a, b, stripe_rows, panel_rows) is merged into its stripe's running lists
+    (skr_topk_merge_rows: one read of the buffer, whatever k is), which start anew at a stripe's first panel and are
+    downloaded after its last; only the finished [stripe, k] lists cross PCIe.  Device memory is stripe_rows x panel_rows
+    floats plus the lists.  The order is total, so the result does not depend on either split.  Operands of either kind
+    (split halves or float32 layout) run the same two steps, as pearson_edges' two-step path does.  Not done here: the
+    self-comparison sweeps all of a x a, not the triangle (r's symmetry is not used), and the selection is a pass of its
+    own over the buffer, not part of the contraction's epilogue."""
     k = _lib.check_topk_k(k)
     ctx = a.ctx
     self_cmp = b is None
@@ -380,22 +428,21 @@ def pearson_topk(a, b=None, k=10, stripe_rows=8192, panel_rows=None):
     out_val = np.full((n, k), np.uint32(_lib.TOPK_PAD_BITS), dtype=np.uint32).view(np.float32)
     if n == 0 or m == 0:
         return out_idx, out_val
-    stripe_rows = max(1, min(int(stripe_rows), n))
-    panel_rows = m if panel_rows is None else max(1, min(int(panel_rows), m))
-    buf = ctx.empty(stripe_rows, panel_rows)
-    idx, val = ctx.empty(stripe_rows, k, np.uint32), ctx.empty(stripe_rows, k, np.float32)
-    for s0 in range(0, n, stripe_rows):
-        rows = min(stripe_rows, n - s0)
-        a_s = a if rows == n else a.view(s0, rows)
-        for p0 in range(0, m, panel_rows):
-            cols = min(panel_rows, m - p0)
-            _lib.pearson_gemm_op(ctx, a_s, b if cols == m else b.view(p0, cols), buf)
-            _lib.topk_merge_rows(ctx, buf, idx, val, k, first=p0 == 0, nrows=rows, col_begin=0, col_end=cols,
-                                 row_global0=s0, col_global0=p0, exclude_diag=self_cmp)
-        idx.to_numpy(0, rows, out=out_idx[s0:s0 + rows])
-        val.to_numpy(0, rows, out=out_val[s0:s0 + rows])
-    for mat in (buf, idx, val):
-        mat.free()
+    with contextlib.ExitStack() as held:  # the sweep's buffer, idx and val: freed however this ends
+        sweep = held.enter_context(Sweep(a, b, stripe_rows, panel_rows))
+        idx = ctx.empty(sweep.stripe_rows, k, np.uint32)
+        held.callback(idx.free)
+        val = ctx.empty(sweep.stripe_rows, k, np.float32)
+        held.callback(val.free)
+
+        def merge(buf, nrows, col_begin, col_end, row_global0, col_global0, upper_only):
+            _lib.topk_merge_rows(ctx, buf, idx, val, k, first=col_global0 == 0, nrows=nrows, col_begin=col_begin,
+                                 col_end=col_end, row_global0=row_global0, col_global0=col_global0, exclude_diag=self_cmp)
+            if col_global0 + col_end - col_begin == m:  # the stripe's last panel
+                idx.to_numpy(0, nrows, out=out_idx[row_global0:row_global0 + nrows])
+                val.to_numpy(0, nrows, out=out_val[row_global0:row_global0 + nrows])
+
+        sweep.run(merge)
     return out_idx, out_val
 
 

@@ -6,13 +6,13 @@ sim[np.triu_indices]); the specification here is numpy on this package's own flo
     np.histogram(values, bins=edges) with the cells below, above and NaN counted apart (np.histogram drops them silently)
     np.sort(values[~isnan(values)])[rank] in the float32 ordering with -0 below +0
 
-count for count and bit for bit (tests/distribution_model.py).  r is produced and consumed one [stripe, panel] block at a
-time, as in consumers.pearson_topk; a block is reduced by skr_hist_edges / skr_hist_key_digits to 64-bit counts that are
-added up on the host.  A cell list or a piece of r is never kept: device memory is one [stripe_rows, panel] buffer.
+count for count and bit for bit (tests/distribution_model.py).  r is produced one [stripe, panel] block at a time by
+consumers.Sweep; a block is reduced by skr_hist_edges / skr_hist_key_digits to 64-bit counts that are added up on the
+host.  A cell list or a piece of r is never kept: device memory is one [stripe_rows, panel] buffer.
 
-An order statistic is a radix descent over the order-preserving key of a float32: DIGITS passes, each one sweep of all
-blocks (r is recomputed), each a histogram of the next key digit among the cells that share the prefix found so far.
-The descent itself runs on the host in Python ints.
+An order statistic is a radix descent over the order-preserving key of a float32 (consumers.float32_key): DIGITS
+passes, each one sweep of all blocks (r is recomputed), each a histogram of the next key digit among the cells that share
+the prefix found so far.  The descent itself runs on the host in Python ints.
 """
 import ctypes as C
 from fractions import Fraction
@@ -20,6 +20,7 @@ from fractions import Fraction
 import numpy as np
 
 from seekr_amd import _lib
+from seekr_amd.consumers import Sweep, block_args, float32_unkey
 
 DIGITS = (12, 10, 10)   # key bits per pass, most significant first
 MAX_PREFIXES = 8        # distinct prefixes one pass takes (skr_hist_key_digits)
@@ -27,12 +28,6 @@ MAX_EDGES = 4097        # edges of one table (skr_hist_edges)
 
 
 # ---- one block ----------------------------------------------------------------------------------------------------------
-def _block_args(r, nrows, col_begin, col_end, row_global0, col_global0, upper_only):
-    nrows = r.rows if nrows is None else nrows
-    col_end = r.cols if col_end is None else col_end
-    return (r.ctx._h, r._h, int(nrows), int(col_begin), int(col_end), int(row_global0), int(col_global0), 1 if upper_only else 0)
-
-
 def check_edges(edges):
     """The edge table as the device takes it: 2 ... MAX_EDGES float32, finite, strictly ascending (ValueError otherwise)."""
     e = np.ascontiguousarray(edges, dtype=np.float32).reshape(-1)
@@ -62,10 +57,10 @@ def hist_edges_block(r, edges, hist, extra, nrows=None, col_begin=0, col_end=Non
                      upper_only=False):
     """Add the cells of the device block r[0:nrows, col_begin:col_end] to hist (uint64 [len(edges) - 1]) and to
     extra = uint64 [3]: below, above, nan (skr_hist_edges)."""
-    _lib.check(_lib.lib().skr_hist_edges(*_block_args(r, nrows, col_begin, col_end, row_global0, col_global0, upper_only),
-                                         edges.ctypes.data_as(C.c_void_p), len(edges), hist.ctypes.data_as(C.c_void_p),
-                                         extra[0:].ctypes.data_as(C.c_void_p), extra[1:].ctypes.data_as(C.c_void_p),
-                                         extra[2:].ctypes.data_as(C.c_void_p)))
+    _lib.check(_lib.lib().skr_hist_edges(*block_args(r, nrows, col_begin, col_end, row_global0, col_global0),
+                                         1 if upper_only else 0, edges.ctypes.data_as(C.c_void_p), len(edges),
+                                         hist.ctypes.data_as(C.c_void_p), extra[0:].ctypes.data_as(C.c_void_p),
+                                         extra[1:].ctypes.data_as(C.c_void_p), extra[2:].ctypes.data_as(C.c_void_p)))
 
 
 def hist_key_block(r, shift, bits, prefixes, prefix_bits, hist, nan, nrows=None, col_begin=0, col_end=None, row_global0=0,
@@ -74,56 +69,16 @@ def hist_key_block(r, shift, bits, prefixes, prefix_bits, hist, nan, nrows=None,
     key digits (skr_hist_key_digits)."""
     p = np.ascontiguousarray(prefixes, dtype=np.uint32)
     assert hist.dtype == np.uint64 and hist.flags.c_contiguous and hist.size == len(p) << bits
-    _lib.check(_lib.lib().skr_hist_key_digits(*_block_args(r, nrows, col_begin, col_end, row_global0, col_global0, upper_only),
-                                              int(shift), int(bits), int(prefix_bits), p.ctypes.data_as(C.c_void_p), len(p),
-                                              hist.ctypes.data_as(C.c_void_p), nan.ctypes.data_as(C.c_void_p)))
+    _lib.check(_lib.lib().skr_hist_key_digits(*block_args(r, nrows, col_begin, col_end, row_global0, col_global0),
+                                              1 if upper_only else 0, int(shift), int(bits), int(prefix_bits),
+                                              p.ctypes.data_as(C.c_void_p), len(p), hist.ctypes.data_as(C.c_void_p),
+                                              nan.ctypes.data_as(C.c_void_p)))
 
 
 # ---- the sweep ----------------------------------------------------------------------------------------------------------
 def n_cells(a, b=None):
     """The cells a sweep visits: the upper triangle (k = 1) of the self-comparison, or all of a x b."""
     return a.rows * (a.rows - 1) // 2 if b is None else a.rows * b.rows
-
-
-class _Sweep:
-    """The blocks of r = a b^T / K, one after another in one reusable [stripe_rows, panel] buffer.  b=None: the
-    self-comparison's upper triangle — pearson_edges' two-step stripe loop, columns from the stripe's first row on,
-    upper_only set; else pearson_cells' loop over all of a x b.  panel_rows cuts the columns of either."""
-
-    def __init__(self, a, b=None, stripe_rows=8192, panel_rows=None):
-        self.a, self.other, self.self_cmp = a, (a if b is None else b), b is None
-        self.ctx = a.ctx
-        n, m = a.rows, self.other.rows
-        self.stripe_rows = max(1, min(int(stripe_rows), max(n, 1)))
-        self.panel_rows = max(m, 1) if panel_rows is None else max(1, min(int(panel_rows), max(m, 1)))
-        self.buf = None
-
-    def run(self, visit):
-        """visit(buf, nrows=, col_begin=, col_end=, row_global0=, col_global0=, upper_only=) for every block."""
-        a, b, ctx = self.a, self.other, self.ctx
-        n, m = a.rows, b.rows
-        if n == 0 or m == 0:
-            return
-        if self.buf is None:
-            self.buf = ctx.empty(self.stripe_rows, self.panel_rows)
-        for s0 in range(0, n, self.stripe_rows):
-            rows = min(self.stripe_rows, n - s0)
-            a_s = a if rows == n else a.view(s0, rows)
-            for p0 in range(s0 if self.self_cmp else 0, m, self.panel_rows):
-                cols = min(self.panel_rows, m - p0)
-                b_p = b if cols == m else b.view(p0, cols)
-                _lib.pearson_gemm_op(ctx, a_s, b_p, self.buf)
-                visit(self.buf, nrows=rows, col_begin=0, col_end=cols, row_global0=s0, col_global0=p0,
-                      upper_only=self.self_cmp)
-                if b_p is not b:
-                    b_p.free()
-            if a_s is not a:
-                a_s.free()
-
-    def free(self):
-        if self.buf is not None:
-            self.buf.free()
-            self.buf = None
 
 
 def r_histogram(a, b=None, edges=None, bins=None, range=None, stripe_rows=8192, panel_rows=None):
@@ -133,21 +88,12 @@ def r_histogram(a, b=None, edges=None, bins=None, range=None, stripe_rows=8192, 
     self-comparison; else every cell of a x b.  edges, or bins with range=(lo, hi) — make_edges."""
     edges = make_edges(edges, bins, range)
     hist, extra = np.zeros(len(edges) - 1, dtype=np.uint64), np.zeros(3, dtype=np.uint64)
-    sweep = _Sweep(a, b, stripe_rows, panel_rows)
-    try:
+    with Sweep(a, b, stripe_rows, panel_rows) as sweep:
         sweep.run(lambda buf, **where: hist_edges_block(buf, edges, hist, extra, **where))
-    finally:
-        sweep.free()
     return hist, int(extra[0]), int(extra[1]), int(extra[2])
 
 
-# ---- the float32 ordering and the descent -------------------------------------------------------------------------------
-def unkey(k):
-    """The float32 whose order-preserving key (significant._key) is the int k."""
-    u = (k ^ 0x80000000) if k & 0x80000000 else (~k & 0xffffffff)
-    return np.uint32(u).view(np.float32)
-
-
+# ---- the descent over the float32 ordering ------------------------------------------------------------------------------
 def descend(ranks, pass_fn):
     """(values float32 [len(ranks)], M) by a radix descent over the key: for each 0-based ascending rank among the
     non-NaN cells, the float32 with exactly that rank.  pass_fn(shift, bits, prefixes, prefix_bits) -> (uint64
@@ -181,7 +127,7 @@ def descend(ranks, pass_fn):
             following.append(((p << bits) | digit, r - below))
         state = following
         done += bits
-    return np.array([unkey(p) for p, _ in state], dtype=np.float32), total
+    return float32_unkey([p for p, _ in state]), total
 
 
 def _check_ranks(ranks):
@@ -213,11 +159,8 @@ def r_order_statistics(a, b=None, ranks=(), stripe_rows=8192, panel_rows=None):
     len(DIGITS) sweeps of all blocks whatever the number of ranks up to MAX_PREFIXES distinct prefixes (more: batches).
     A rank outside [0, M) raises ValueError after the first sweep.  Nothing is allocated in proportion to M."""
     ranks = _check_ranks(ranks)
-    sweep = _Sweep(a, b, stripe_rows, panel_rows)
-    try:
+    with Sweep(a, b, stripe_rows, panel_rows) as sweep:
         return _order_statistics(sweep, ranks)[0]
-    finally:
-        sweep.free()
 
 
 def quantile_rank(q, m):
@@ -246,11 +189,8 @@ def r_quantiles(a, b=None, q=(), stripe_rows=8192, panel_rows=None):
     q = list(np.atleast_1d(q).tolist()) if not isinstance(q, (list, tuple)) else list(q)
     for x in q:
         quantile_rank(x, 1)  # the range check, before any sweep
-    sweep = _Sweep(a, b, stripe_rows, panel_rows)
-    try:
+    with Sweep(a, b, stripe_rows, panel_rows) as sweep:
         values, m, _ = _order_statistics(sweep, lambda m: [quantile_rank(x, m) for x in q])
-    finally:
-        sweep.free()
     return values, m
 
 
@@ -259,11 +199,8 @@ def density_cutoff(a, density, b=None, stripe_rows=8192, panel_rows=None):
     floor(Fraction(density) M)) — at least m cells are >= c and fewer than m are > c.  pearson_edges(a, c) then holds at
     least m edges (ties with c are kept; cells equal to 0 are dropped by the edge rule, so choose a density with c > 0)."""
     density_rank(density, 1)
-    sweep = _Sweep(a, b, stripe_rows, panel_rows)
-    try:
+    with Sweep(a, b, stripe_rows, panel_rows) as sweep:
         values, _, _ = _order_statistics(sweep, lambda m: [density_rank(density, m)])
-    finally:
-        sweep.free()
     return values[0]
 
 
@@ -298,8 +235,7 @@ def distribution(a, b=None, edges=None, bins=None, range=None, q=(), densities=(
     if want_hist:
         edges = make_edges(edges, bins, range)
     out = {}
-    sweep = _Sweep(a, b, stripe_rows, panel_rows)
-    try:
+    with Sweep(a, b, stripe_rows, panel_rows) as sweep:
         if want_hist:
             hist, extra = np.zeros(len(edges) - 1, dtype=np.uint64), np.zeros(3, dtype=np.uint64)
             sweep.run(lambda buf, **where: hist_edges_block(buf, edges, hist, extra, **where))
@@ -310,8 +246,6 @@ def distribution(a, b=None, edges=None, bins=None, range=None, q=(), densities=(
             values, m, nan = _order_statistics(
                 sweep, lambda m: [quantile_rank(x, m) for x in q] + [density_rank(d, m) for d in densities])
             out.update(q=q, quantiles=values[:len(q)], densities=densities, cutoffs=values[len(q):])
-    finally:
-        sweep.free()
     return RDistribution(n_cells(a, b), m, nan, **out)
 
 

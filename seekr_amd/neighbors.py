@@ -4,8 +4,8 @@ of another (or of itself) it correlates with most.  The reference has no such fu
     idx[i], val[i] == the first k entries of np.argsort(-r[i], kind="stable") and their r, r = pearson(counts1, counts2)
     as this package computes it in float32, NaN last, row i's own cell left out of the self-comparison.
 
-r is produced and consumed one [stripe, panel] block at a time (consumers.pearson_topk), so 10^6 rows need the operands
-and a block buffer on the device, not 4 TB.
+r is produced one [stripe, panel] block at a time (consumers.Sweep) and consumed by consumers.pearson_topk, so 10^6 rows
+need the operands and a block buffer on the device, not 4 TB.
 """
 import numpy as np
 

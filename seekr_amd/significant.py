@@ -49,14 +49,12 @@ class SignificantPairs:
 
 # ---- the float32 ordering ---------------------------------------------------------------------------------------------
 def _key(x):
-    """float32 -> int whose order is the order of the values (-0.0 just below +0.0)."""
-    u = int(np.float32(x).view(np.uint32))
-    return (~u & 0xffffffff) if u & 0x80000000 else (u | 0x80000000)
+    """float32 -> int whose order is the order of the values (-0.0 just below +0.0): consumers.float32_key of a scalar."""
+    return int(consumers.float32_key(np.float32(x))[0])
 
 
 def _unkey(k):
-    u = (k ^ 0x80000000) if k & 0x80000000 else (~k & 0xffffffff)
-    return np.uint32(u).view(np.float32)
+    return consumers.float32_unkey(k)[()]
 
 
 def float32_steps(x, steps):

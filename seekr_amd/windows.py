@@ -16,6 +16,7 @@ import numpy as np
 
 from seekr_amd import _lib
 from seekr_amd import pearson as pearson_mod
+from seekr_amd.consumers import float32_key, float32_unkey
 from seekr_amd.fasta_reader import Reader
 from seekr_amd.kmer_counts import NAN_WARNING, BasicCounter, _as_device_vector
 
@@ -365,21 +366,10 @@ def _significant_cells(run, fitres, bestfit, name, alpha):
             m.free()
 
 
-def _key32(v):
-    """float32 array -> uint32 keys whose order is the order of the values, -0 just below +0 (significant._key)."""
-    u = np.ascontiguousarray(v, dtype=np.float32).view(np.uint32)
-    return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
-
-
-def _unkey32(key):
-    key = np.asarray(key, dtype=np.uint32)
-    return np.where(key & np.uint32(0x80000000), key ^ np.uint32(0x80000000), ~key).astype(np.uint32).view(np.float32)
-
-
 def merge_pieces(row, first, last, n_hot, peak, peak_col, seq_index, max_gap):
     """The hits of a list of pieces, in any order: (row, first, last, n_hot, peak, peak_col) arrays ordered by (row, first).
     Two pieces of one row and one sequence (seq_index[first]) are joined iff first_b - last_a - 1 <= max_gap, the pieces
-    taken sorted by (row, first); n_hot adds up, the peak is the larger key (_key32), the earlier window on equal keys.
+    taken sorted by (row, first); n_hot adds up, the peak is the larger key (float32_key), the earlier window on equal keys.
     Applied to the pieces of ANY tiling of the cells this gives the hits of the cells, which is why tiles, chunks and
     launches need no carry.  Vectorised: one lexsort and three reduceat."""
     row, first, last = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (row, first, last))
@@ -396,9 +386,9 @@ def merge_pieces(row, first, last, n_hot, peak, peak_col, seq_index, max_gap):
     begin = np.flatnonzero(~join)
     end = np.append(begin[1:], len(row)) - 1
     # (key << 32) | (0xFFFFFFFF - window): the largest key, then the earliest window
-    packed = (_key32(peak).astype(np.uint64) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - peak_col.astype(np.uint64))
+    packed = (float32_key(peak).astype(np.uint64) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - peak_col.astype(np.uint64))
     best = np.maximum.reduceat(packed, begin)
-    return (row[begin], first[begin], last[end], np.add.reduceat(n_hot, begin), _unkey32((best >> np.uint64(32)).astype(np.uint32)),
+    return (row[begin], first[begin], last[end], np.add.reduceat(n_hot, begin), float32_unkey((best >> np.uint64(32)).astype(np.uint32)),
             (np.uint64(0xFFFFFFFF) - (best & np.uint64(0xFFFFFFFF))).astype(np.int64))
 
 

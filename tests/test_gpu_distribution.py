@@ -292,7 +292,7 @@ def prepared(name):
 @functools.lru_cache(maxsize=None)
 def reference_values(name):
     """The counted cells of r, downloaded block by block through the sweep's own pearson_gemm_op calls (unsplit)."""
-    from seekr_amd import distribution
+    from seekr_amd import consumers
     z, z2 = prepared(name)
     parts = []
 
@@ -300,7 +300,7 @@ def reference_values(name):
         m = np.array(buf.to_numpy(0, nrows))
         parts.append(counted(m, nrows, col_begin, col_end, row_global0, col_global0, upper_only).copy())
 
-    sweep = distribution._Sweep(z, z2)
+    sweep = consumers.Sweep(z, z2)
     sweep.run(visit)
     sweep.free()
     values = np.concatenate(parts)
@@ -389,7 +389,7 @@ def test_density_cutoff_is_the_edge_count():
     c[40] = c[41]
     z, _ = neighbors._prepare(ctx, c, c, True)
     parts = []
-    sweep = distribution._Sweep(z)
+    sweep = consumers.Sweep(z)
     sweep.run(lambda buf, nrows, col_begin, col_end, row_global0, col_global0, upper_only: parts.append(
         counted(np.array(buf.to_numpy(0, nrows)), nrows, col_begin, col_end, row_global0, col_global0, upper_only).copy()))
     sweep.free()

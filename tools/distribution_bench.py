@@ -135,7 +135,7 @@ def sweeps(ctx, z, runs):
     m = distribution.n_cells(z)
     ranks1, ranks8 = [m // 2], [int(m * q) for q in (0.001, 0.01, 0.1, 0.25, 0.5, 0.75, 0.99, 0.999)]
     edges = distribution.make_edges(None, 200, (-1, 1))
-    sweep = distribution._Sweep(z, None, STRIPE)
+    sweep = consumers.Sweep(z, None, STRIPE)
     arms = {
         "plain": lambda: sweep.run(lambda buf, **where: None),
         "order_statistics_1": lambda: distribution.r_order_statistics(z, ranks=ranks1, stripe_rows=STRIPE),
@@ -187,7 +187,7 @@ def route(ctx, z, runs):
         return np.partition(host, rank)[rank]
 
     def no_matrix(peak):
-        sweep = distribution._Sweep(z, None, STRIPE)
+        sweep = consumers.Sweep(z, None, STRIPE)
         try:
             values, _, _ = distribution._order_statistics(sweep, lambda m: [distribution.quantile_rank(q, m)])
             ctx.sync()

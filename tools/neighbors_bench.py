@@ -7,7 +7,7 @@ For panel_rows in 8 192, 32 768 and None (all of b) and k in 1, 10, 64, KMAX —
 and panels, ending in a device synchronise, median of --runs after one warm-up, the three arms alternating:
   a   the contraction of every [stripe, panel] block into the reusable buffer, no selection
   b   a, each stripe followed by skr_topk_rows (k passes over the stripe; it cannot merge, so whole-width panels only)
-  c   a, each block followed by skr_topk_merge_rows (consumers.pearson_topk's loop without the download)
+  c   a, each block followed by skr_topk_merge_rows (what consumers.pearson_topk does to each block, without the download)
 and the device time of the two selection kernels themselves (the library's event timers), which does not depend on a
 difference of two wall times.  `read_once_ms`: the time one read of all of r's cells takes at the copy bandwidth measured
 here (a device-to-device copy of 1 GiB moves 2 GiB; skr_peer_copy_rows within one GPU).  The acceptance condition of the kernel (DESIGN_KERNELS.md) is
