@@ -579,6 +579,49 @@ int skr_topk_merge_rows(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t c
  * buffer and the list are sorted together before a sweep step of 1 024 cells that might not fit).  Either may be NULL. */
 int skr_topk_merge_limits(int* kmax, int* candidate_cap);
 
+/* Per-COLUMN top-k in one pass, with a running result: skr_topk_merge_rows turned by 90 degrees.  After the call
+ * io_idx[j - col_begin, :] / io_val[j - col_begin, :] hold, for col_begin <= j < col_end, the k best entries of the union
+ * of (a) the list they held on entry — ignored when first != 0; a slot with index 0xFFFFFFFF is no entry — and (b) the
+ * cells r[0:nrows, j], minus the cell whose global row equals its global column when exclude_diag != 0.  Entries are
+ * GLOBAL ROWS (row_global0 + i).  Order: skr_topk_merge_rows' with the global row in the place of the column — value
+ * descending, -0 == +0, NaN after every number, ties to the smaller global row: the result equals skr_topk_merge_rows on
+ * the transposed block with row_global0 and col_global0 swapped.  The order is total, so a column merged stripe by
+ * stripe ends with the same list whatever the split.  Values keep the cells' own bits; unfilled slots are 0xFFFFFFFF /
+ * NaN (0x7FC00000).  *saw_nan as in skr_topk_merge_rows (NULL: the call does not wait for the device).  Every cell is
+ * read once, whatever k is, in runs of 128 bytes along the rows; no transposed copy is written; rows may start at any
+ * offset from a 16-byte boundary.  1 <= k <= kmax of skr_topk_merge_cols_limits and global rows and columns below
+ * 0xFFFFFFFF, else SKR_ERR_INVALID.  io_idx: SKR_U32, io_val: SKR_F32, each at least (col_end - col_begin) * k cells,
+ * column j at (j - col_begin) * k.                                                                                   */
+int skr_topk_merge_cols(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t col_begin, int64_t col_end,
+                        int64_t row_global0, int64_t col_global0, int exclude_diag, int k, int first,
+                        skr_mat* io_idx, skr_mat* io_val, int* saw_nan);
+/* The constants of skr_topk_merge_cols' kernel: the largest k, the columns a workgroup owns, the rows of one sweep step,
+ * and the candidates ONE COLUMN's segment holds (every column with candidates is merged into its list before a step
+ * that might not fit into some segment).  Any may be NULL.                                                          */
+int skr_topk_merge_cols_limits(int* kmax, int* strip_cols, int* rows_step, int* candidate_cap);
+
+/* Top-k lists -> nearest-neighbour PAIRS.  idx_a / val_a [n1, ka] (SKR_U32 / SKR_F32): row i's list, entries index set
+ * B; idx_b / val_b [n2, kb]: row j's list, entries index set A.  idx_b = val_b = NULL is the SELF form: one set, idx_a
+ * serves both sides and every pair is written once with row < col.
+ * Candidates: entry t of row i of idx_a with j = idx_a[i, t] != 0xFFFFFFFF and a value that is not NaN is the candidate
+ * (i, j) with rank_row = t; entry t of row j of idx_b with i = idx_b[j, t], under the same conditions, the candidate
+ * (i, j) with rank_col = t.  Self form: entry t of row u with v = idx_a[u, t], v != u, is a candidate for the pair
+ * (min(u, v), max(u, v)); read from row min it carries rank_row, read from row max rank_col.
+ * mode 0 (mutual): the pairs that have both candidates; mode 1 (union): those that have either.  A pair's value is the
+ * bits of its rank_row candidate when there is one, else those of its rank_col candidate; a missing rank is 0xFFFFFFFF.
+ * positive_only != 0: a pair whose value is not > 0 is not written (what skr_leiden's graph needs).
+ * Per pair, at cells out_offset ... out_offset + *count - 1 of five vectors: out_rows, out_cols (SKR_U32), out_vals
+ * (SKR_F32), out_rank_row, out_rank_col (SKR_U32), in ascending (row, col) order, the same bytes on every run.  *count
+ * receives the number of pairs.  If out_offset + *count exceeds the capacity of any output nothing is written and the
+ * call still returns SKR_OK with the count: the caller grows its buffers and calls again (skr_select_cells_ge's
+ * contract).  With all five NULL only the count is made; some but not all NULL: SKR_ERR_INVALID.
+ * Precondition: the lists are as the merge kernels leave them — no index twice in one list (not detected).  An index
+ * >= n2 in idx_a (>= n1 in the self form, or in idx_b) is never used as an address: the call returns SKR_ERR_INVALID.
+ * At most 2^31 - 1 list slots per call.  The call waits for the device.                                             */
+int skr_knn_pairs(skr_ctx* ctx, const skr_mat* idx_a, const skr_mat* val_a, const skr_mat* idx_b, const skr_mat* val_b,
+                  int mode, int positive_only, skr_mat* out_rows, skr_mat* out_cols, skr_mat* out_vals,
+                  skr_mat* out_rank_row, skr_mat* out_rank_col, int64_t out_offset, int64_t* count);
+
 /* ---------------------------------------------------------------- the k-mers behind a similarity -- */
 /* r[i, j] is the mean over the columns w of z1[i, w] * z2[j, w]; this lists, for each of n_pairs pairs (rows[e], cols[e])
  * (SKR_U32 vectors), the `top` columns whose term c[w] = float32(z1[rows[e], w] * z2[cols[e], w]) is largest (largest != 0)

@@ -136,6 +136,9 @@ SIGNATURES = {
     "skr_topk_rows": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _int, _p, _p]),
     "skr_topk_merge_rows": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _p, _p, C.POINTER(_int)]),
     "skr_topk_merge_limits": (_int, [C.POINTER(_int), C.POINTER(_int)]),
+    "skr_topk_merge_cols": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _p, _p, C.POINTER(_int)]),
+    "skr_topk_merge_cols_limits": (_int, [C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), C.POINTER(_int)]),
+    "skr_knn_pairs": (_int, [_p, _p, _p, _p, _p, _int, _int, _p, _p, _p, _p, _p, _i64, C.POINTER(_i64)]),
     "skr_pair_kmers": (_int, [_p, _p, _p, _p, _p, _i64, _int, _int, _p, _p, _p, _p, C.POINTER(_i64)]),
     "skr_group_colstat": (_int, [_p, _p, _p, _p, _i64, _p, _p]),
     "skr_leiden": (_int, [_p, _p, _p, _p, _i64, _i64, _int, C.c_double, _int, _int, _p, C.POINTER(C.c_double), C.POINTER(_i64),
@@ -1174,6 +1177,41 @@ def topk_merge_rows(ctx, r, idx, val, k, first, nrows=None, col_begin=0, col_end
     (False without want_nan: the call then does not wait for the device)."""
     nan = _int(0)
     check(lib().skr_topk_merge_rows(*block_args(r, nrows, col_begin, col_end, row_global0, col_global0),
+                                    1 if exclude_diag else 0, int(k), 1 if first else 0, idx._h, val._h,
+                                    C.byref(nan) if want_nan else None))
+    return bool(nan.value)
+
+
+# what skr_topk_merge_cols_limits reports (csrc/topk_cols.hip: kColsKmax, kColsStrip, kColsStep, kColsCap), mirrored as
+# the row kernel's constants are
+TOPK_COLS_KMAX = 64     # largest k of skr_topk_merge_cols: one list slot per lane of the merging wave
+TOPK_COLS_STRIP = 32    # columns a workgroup owns
+TOPK_COLS_STEP = 16     # rows per sweep step
+TOPK_COLS_CAP = 64      # candidates one column's segment holds: merged when more than CAP - STEP wait in some column
+
+
+def topk_merge_cols_limits():
+    """(kmax, strip_cols, rows_step, candidate_cap) as the library reports them."""
+    out = [_int(0) for _ in range(4)]
+    check(lib().skr_topk_merge_cols_limits(*[C.byref(v) for v in out]))
+    return tuple(v.value for v in out)
+
+
+def check_topk_cols_k(k, what="k"):
+    """ValueError unless 1 <= k <= TOPK_COLS_KMAX (no device call)."""
+    if int(k) != k or not 1 <= int(k) <= TOPK_COLS_KMAX:
+        raise ValueError("{} must be an integer in 1..{} (got {!r})".format(what, TOPK_COLS_KMAX, k))
+    return int(k)
+
+
+def topk_merge_cols(ctx, r, idx, val, k, first, nrows=None, col_begin=0, col_end=None, row_global0=0, col_global0=0,
+                    exclude_diag=True, want_nan=False):
+    """skr_topk_merge_cols: per column of r[0:nrows, col_begin:col_end] the k best of (the lists in idx / val, unless
+    `first`) and the column's cells, entries being global rows, into idx / val (uint32 / float32 device matrices of at
+    least (col_end - col_begin) * k cells, column j at (j - col_begin) * k).  Returns saw_nan (False without want_nan:
+    the call then does not wait for the device)."""
+    nan = _int(0)
+    check(lib().skr_topk_merge_cols(*block_args(r, nrows, col_begin, col_end, row_global0, col_global0),
                                     1 if exclude_diag else 0, int(k), 1 if first else 0, idx._h, val._h,
                                     C.byref(nan) if want_nan else None))
     return bool(nan.value)

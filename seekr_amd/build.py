@@ -15,7 +15,7 @@ LIB = os.path.join(HERE, "libseekr_hip.so")
 DIAG_LIB = os.path.join(HERE, "libseekr_hip_diag.so")
 DIAG_SOURCES = ["pearson_bf16.hip"]  # compiled a second time with -DSEEKR_DIAG for the diagnostic library
 SOURCES = ["ctx.hip", "pack.hip", "count.hip", "windows.hip", "normalize.hip", "normalize_any.hip", "pearson.hip", "pearson_bf16.hip", "operand.hip",
-           "consumers.hip", "cells.hip", "domain_hits.hip", "distribution.hip", "topk.hip", "explain.hip", "fused_edges.hip", "adjust.hip", "leiden.hip", "comm.hip", "io.hip", "csv_read.hip", "host_api.hip"]
+           "consumers.hip", "cells.hip", "domain_hits.hip", "distribution.hip", "topk.hip", "topk_cols.hip", "knn_pairs.hip", "explain.hip", "fused_edges.hip", "adjust.hip", "leiden.hip", "comm.hip", "io.hip", "csv_read.hip", "host_api.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-I" + os.path.join(HERE, "..", "include")]

@@ -97,6 +97,23 @@ Examples
     three of b.npy for each of a.npy:  seekr_nearest a.npy b.npy -n 3 -o nearest.csv -bi
 """
 
+RECIPROCAL_HITS_DOC = """
+Description
+-----------
+The reciprocal nearest neighbours of the rows of two k-mer count files (or of one), computed on an MI355X from ONE sweep of
+the correlations and without the all-pairs matrix: the pairs (row, col) where col is among the K rows of the second file
+row correlates with most and (mutual) or or (union) row is among the K rows of the first file col correlates with most.
+The output is a CSV with the columns row,col,r,rank_row,rank_col, ascending by row and col: rank 0 is the best
+neighbour, an empty rank means the pair is not in that side's list (union only); rows and columns are named by the
+labels of the count files, or by their indices for .npy input.  With one count file a row is not its own neighbour and
+every pair comes once, the smaller row first.
+
+Examples
+--------
+    mutual best hits of two files:        seekr_reciprocal_hits a.csv b.csv -n 1 -o hits.csv
+    union 15-neighbour pairs of one file:  seekr_reciprocal_hits counts.npy -n 15 -m union -o pairs.csv -bi
+"""
+
 SIGNIFICANT_PAIRS_DOC = """
 Description
 -----------
@@ -341,6 +358,42 @@ def console_nearest():
     _run_nearest(args.counts1, args.counts2, int(args.neighbors), args.outfile, args.binary_input)
 
 
+def _run_reciprocal_hits(counts1, counts2, neighbors, mode, outfile, binary_input):
+    import csv
+    from seekr_amd import reciprocal
+    names1 = names2 = None
+    same_file = counts2 is None or counts1 == counts2
+    if binary_input:  # read as _run_nearest reads them
+        counts1 = np.load(counts1)
+        counts2 = None if same_file else np.load(counts2)
+    else:
+        counts1, names1 = _read_labelled_csv(counts1)
+        counts2, names2 = (None, names1) if same_file else _read_labelled_csv(counts2)
+    hits = reciprocal.reciprocal_hits(counts1, counts2, k=neighbors, mode=mode)
+    with open(outfile, "w", newline="") as f:
+        out = csv.writer(f, lineterminator="\n")
+        out.writerow(list(reciprocal.COLUMNS))
+        for i, j, r, rank_row, rank_col in zip(*(hits[c].to_numpy() for c in reciprocal.COLUMNS)):
+            out.writerow([int(i) if names1 is None else names1[int(i)], int(j) if names2 is None else names2[int(j)], str(r),
+                          "" if rank_row == _lib.TOPK_PAD_IDX else int(rank_row),
+                          "" if rank_col == _lib.TOPK_PAD_IDX else int(rank_col)])
+
+
+def console_reciprocal_hits():
+    parser = argparse.ArgumentParser(usage=RECIPROCAL_HITS_DOC, formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    parser.add_argument("counts1", help="Count file whose rows are the `row` side.")
+    parser.add_argument("counts2", nargs="?", default=None,
+                        help="Count file whose rows are the `col` side (default: counts1 itself, every pair once).")
+    parser.add_argument("-n", "--neighbors", default=10,
+                        help="Neighbours per row (at most %d with two files, %d with one)." % (_lib.TOPK_COLS_KMAX, _lib.TOPK_MERGE_KMAX))
+    parser.add_argument("-m", "--mode", default="mutual", choices=["mutual", "union"],
+                        help="Keep a pair when both sides list each other (mutual) or when either does (union).")
+    parser.add_argument("-o", "--outfile", default="reciprocal_hits.csv", help="Where the pairs go (CSV: row,col,r,rank_row,rank_col).")
+    parser.add_argument("-bi", "--binary_input", action="store_true", help="The count files are .npy, not labelled CSV.")
+    args = _parse_args_or_exit(parser)
+    _run_reciprocal_hits(args.counts1, args.counts2, int(args.neighbors), args.mode, args.outfile, args.binary_input)
+
+
 def _read_background(path):
     """A 1-D array of background similarities: a .npy file or a one-column CSV (what find_dist writes with
     fit_model=False and an outputname)."""
@@ -570,6 +623,7 @@ Examples
     communities at r >= 0.05, CSV files:   seekr_kmer_leiden seqs.fa mean.npy std.npy 4 -pco 0.05 -cf out
     modularity, kept edges only:           seekr_kmer_leiden seqs.fa mean.npy std.npy 6 -a ModularityVertexPartition -cf out --edges nonzero
     the strongest 0.1 %% of the pairs:     seekr_kmer_leiden seqs.fa mean.npy std.npy 6 -d 0.001 -cf out
+    the union 15-nearest-neighbour graph:  seekr_kmer_leiden seqs.fa mean.npy std.npy 6 -nn 15 -cf out --edges nonzero
 """
 
 
@@ -599,8 +653,14 @@ def console_kmer_leiden():
                         help="with --csvfile: also write _kmers_leiden.csv, this many top k-mers (by mean count) per community.")
     parser.add_argument("-d", "--density", default=None,
                         help="instead of -pco: keep this fraction of the pairs, the most correlated ones (the cutoff is found on the device).")
+    parser.add_argument("-nn", "--knn", default=None,
+                        help="instead of -pco / -d: the graph of every sequence's this many nearest neighbours (positive r only).")
+    parser.add_argument("-nm", "--knn_mode", default="union", choices=["mutual", "union"],
+                        help="with -nn: keep a pair when either (union) or both (mutual) of its ends lists the other.")
     args = _parse_args_or_exit(parser)
     options = {} if args.density is None else {"density": args.density}
+    if args.knn is not None:
+        options.update(knn=int(args.knn), knn_mode=args.knn_mode)
     kmer_leiden.kmer_leiden(args.fasta, args.mean_path, args.std_path, int(args.kmer), args.algo, float(args.rs), float(args.pearsoncutoff),
                             args.setseed, args.edgecolormethod, float(args.edgethreshold), int(args.labelfontsize), args.plotname,
                             args.csvfile, edges=args.edges, kmers_top=None if args.kmers_top is None else int(args.kmers_top), **options)

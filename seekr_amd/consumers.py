@@ -13,6 +13,10 @@ it: keeping these reductions on the GPU avoids shipping an N x N m
     select_cells / pearson_cells  —              the cells with !(r < cutoff) as a device list; pearson_cells over a Sweep
     topk_rows / pearson_topk  —                  the k most correlated rows of every row; pearson_topk merges a Sweep's
                                                  blocks into running lists
+    topk_merge_cols / pearson_topk_both  —       the k most correlated rows of every COLUMN, merged beside the row lists in
+                                                 one Sweep: both directions of a two-set comparison from one r
+    knn_pairs / PairList  —                      top-k lists as mutual or union nearest-neighbour pairs with their ranks, a
+                                                 device list (seekr_amd.reciprocal: reciprocal_hits, knn_graph)
     adjust_pvalues        adj_pval.py:53-138     multipletests on the p-value matrix (symmetric: upper triangle)
     adjust_pvalues_head   —                      the same for the smallest p-values of a longer list (seekr_amd.significant)
     select_le / gather_index  —                  the positions of a vector with value <= bound, and a gather by them
@@ -444,6 +448,117 @@ def pearson_topk(a, b=None, k=10, stripe_rows=8192, panel_rows=None):
 
         sweep.run(merge)
     return out_idx, out_val
+
+
+topk_merge_cols = _lib.topk_merge_cols  # skr_topk_merge_cols, next to _lib.topk_merge_rows
+
+
+def pearson_topk_both(a, b, k=10, stripe_rows=8192, panel_rows=None, keep_device=False):
+    """(idx_a uint32 [a.rows, k], val_a float32 [a.rows, k], idx_b uint32 [b.rows, k], val_b float32 [b.rows, k]) from ONE
+    Sweep(a, b, stripe_rows, panel_rows): the row lists are pearson_topk(a, b, k)'s, byte for byte (every block goes
+    through skr_topk_merge_rows exactly as there), and the column lists are, for every row j of `b`, the k rows of `a` it
+    correlates with most in the same order, ties to the smaller row of a — every block also goes through
+    skr_topk_merge_cols on a row view of resident [b.rows, k] lists, which start anew on the first stripe.  Both lists
+    of a pair (i, j) hold the bits of the one r[i, j] the sweep made, which two sweeps (a x b, then b x a) do not promise.
+    The order is total, so neither list depends on either split.  Device memory: pearson_topk's plus the [b.rows, k]
+    column lists and, with keep_device, [a.rows, k] row lists.  keep_device=True: the four lists come back as device
+    matrices (_lib.Matrix) the caller frees, and nothing is downloaded.  1 <= k <= _lib.TOPK_COLS_KMAX."""
+    k = _lib.check_topk_cols_k(k)
+    ctx = a.ctx
+    n, m = a.rows, b.rows
+    pad_val = np.uint32(_lib.TOPK_PAD_BITS)
+    if n == 0 or m == 0:
+        if keep_device:
+            raise ValueError("keep_device needs rows on both sides (got {} and {})".format(n, m))
+        return (np.full((n, k), _lib.TOPK_PAD_IDX, dtype=np.uint32), np.full((n, k), pad_val, dtype=np.uint32).view(np.float32),
+                np.full((m, k), _lib.TOPK_PAD_IDX, dtype=np.uint32), np.full((m, k), pad_val, dtype=np.uint32).view(np.float32))
+    out = []
+    try:
+        with contextlib.ExitStack() as held:  # the sweep's buffer and the stripe's row lists: freed however this ends
+            sweep = held.enter_context(Sweep(a, b, stripe_rows, panel_rows))
+            for rows, dtype in ((m, np.uint32), (m, np.float32)) + (((n, np.uint32), (n, np.float32)) if keep_device else ()):
+                out.append(ctx.empty(rows, k, dtype))
+            cidx, cval = out[0], out[1]
+            if keep_device:
+                all_idx, all_val = out[2], out[3]
+                out_idx = out_val = None
+            else:
+                idx = ctx.empty(sweep.stripe_rows, k, np.uint32)
+                held.callback(idx.free)
+                val = ctx.empty(sweep.stripe_rows, k, np.float32)
+                held.callback(val.free)
+                out_idx = np.full((n, k), _lib.TOPK_PAD_IDX, dtype=np.uint32)
+                out_val = np.full((n, k), pad_val, dtype=np.uint32).view(np.float32)
+
+            def merge(buf, nrows, col_begin, col_end, row_global0, col_global0, upper_only):
+                where = dict(nrows=nrows, col_begin=col_begin, col_end=col_end, row_global0=row_global0,
+                             col_global0=col_global0, exclude_diag=False)
+                cols = col_end - col_begin
+                if keep_device:  # the stripe's rows of the resident row lists
+                    ridx, rval = all_idx.view(row_global0, nrows), all_val.view(row_global0, nrows)
+                else:
+                    ridx, rval = idx, val
+                pidx, pval = cidx.view(col_global0, cols), cval.view(col_global0, cols)
+                try:
+                    _lib.topk_merge_rows(ctx, buf, ridx, rval, k, first=col_global0 == 0, **where)
+                    _lib.topk_merge_cols(ctx, buf, pidx, pval, k, first=row_global0 == 0, **where)
+                finally:
+                    for v in (pidx, pval) + ((ridx, rval) if keep_device else ()):
+                        v.free()
+                if not keep_device and col_global0 + cols == m:  # the stripe's last panel
+                    idx.to_numpy(0, nrows, out=out_idx[row_global0:row_global0 + nrows])
+                    val.to_numpy(0, nrows, out=out_val[row_global0:row_global0 + nrows])
+
+            sweep.run(merge)
+        if keep_device:
+            return out[2], out[3], out[0], out[1]
+        res = out_idx, out_val, np.array(cidx.to_numpy()), np.array(cval.to_numpy())
+    except BaseException:
+        for x in out:
+            x.free()
+        raise
+    for x in out:
+        x.free()
+    return res
+
+
+class PairList(CellList):
+    """CellList's five-vector sibling: the pairs knn_pairs leaves on the device — row, col (uint32), value (float32),
+    rank_row, rank_col (uint32; 0xFFFFFFFF = the pair is not in that side's list).  It grows by the same
+    count-then-write contract; its first three vectors are an edge list as leiden.communities takes it."""
+    DTYPES = (np.uint32, np.uint32, np.float32, np.uint32, np.uint32)
+
+    def to_host(self):
+        """The filled part as five host arrays (copies); empty arrays for an empty list."""
+        if not self.n:
+            return tuple(np.empty(0, t) for t in self.DTYPES)
+        return tuple(np.array(m.to_numpy(0, self.n)).reshape(-1) for m in self.bufs)
+
+
+KNN_MODES = {"mutual": 0, "union": 1}
+
+
+def knn_mode(mode):
+    """0 / 1 for "mutual" / "union"; ValueError otherwise (no device call)."""
+    if mode not in KNN_MODES:
+        raise ValueError("mode is 'mutual' or 'union' (got {!r})".format(mode))
+    return KNN_MODES[mode]
+
+
+def knn_pairs(idx_a, val_a, idx_b=None, val_b=None, mode="mutual", positive_only=False, into=None):
+    """Append the nearest-neighbour pairs of top-k lists on the device (skr_knn_pairs) to the PairList `into`; returns
+    their number.  idx_a / val_a [n1, k]: row lists whose entries index set B; idx_b / val_b [n2, k]: column lists
+    whose entries index set A (pearson_topk_both's four lists, keep_device=True).  idx_b = val_b = None: the self form —
+    one set, every pair once with row < col.  mode "mutual": pairs in both lists; "union": in either.  A pair's value is
+    its row-list entry's bits when there is one, else its column-list entry's; padded slots and NaN values never pair;
+    positive_only drops pairs whose value is not > 0.  Pairs come in ascending (row, col) order.  into=None: only the
+    count is made."""
+    code = knn_mode(mode)
+    if (idx_b is None) != (val_b is None):
+        raise ValueError("pass idx_b and val_b, or neither")
+    head = (idx_a.ctx._h, idx_a._h, val_a._h, None if idx_b is None else idx_b._h, None if val_b is None else val_b._h, code,
+            1 if positive_only else 0)
+    return _count_then_write(into, 5, lambda *tail: _lib.lib().skr_knn_pairs(*head, *tail[:-1]))[0]
 
 
 FUSE_MAX_DENSITY = 1e-3  # edges per cell above which the fused epilogue costs more than writing the stripe (measured: 100 000 rows, k = 6)

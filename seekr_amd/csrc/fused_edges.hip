@@ -8,53 +8,16 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "edge_pass.hpp"
 #include "radix.hpp"
-
-namespace {
 
 // ---------------------------------------------------------------------------------------------------------------
 // LSD radix sort of (key = row << 32 | column, value) pairs, 8 bits per pass, only over the bits that can be set:
 // ceil(bits(N) / 8) passes over the column field, then ceil(bits(M) / 8) over the row field (rows taken relative to
 // the block's first row).  The kernels, the chunk rule and the pass itself are radix.hpp's; here are the policy (what a
-// key is, what travels with it, where the last pass writes), the workspace and the pass loop.
+// key is, what travels with it, where the last pass writes: edge_pass.hpp's EdgePass, shared with knn_pairs.hip), the
+// workspace and the pass loop.
 // ---------------------------------------------------------------------------------------------------------------
-using skr_radix::kDigits;
-
-// the sort's policy (radix.hpp): the value travels with the key, and the LAST pass splits the key into the caller's
-// row and column arrays
-template <bool LAST>
-struct EdgePass {
-    using Count = uint32_t;  // the list is below 2^31
-    struct Item {
-        unsigned long long key;
-        float val;
-    };
-    const unsigned long long* keys_in;
-    const float* vals_in;
-    unsigned long long* keys_out;  // middle passes
-    float* vals_out;               // every pass (the last one: the caller's value array)
-    uint32_t* rows_out;            // last pass only
-    uint32_t* cols_out;
-    uint32_t row0;  // subtracted from the row field before a row digit is taken
-    int shift;      // within the field
-    int row_field;  // 0: digit from the column field, 1: from the row field
-    __device__ __forceinline__ Item load(int64_t i) const { return Item{keys_in[i], vals_in[i]}; }
-    __device__ __forceinline__ uint32_t digit(const Item& it) const {
-        const uint32_t f = row_field ? (uint32_t)(it.key >> 32) - row0 : (uint32_t)it.key;
-        return (f >> shift) & (kDigits - 1);
-    }
-    __device__ __forceinline__ void store(uint32_t pos, const Item& it) const {
-        if (LAST) {
-            rows_out[pos] = (uint32_t)(it.key >> 32);
-            cols_out[pos] = (uint32_t)it.key;
-        } else {
-            keys_out[pos] = it.key;
-        }
-        vals_out[pos] = it.val;
-    }
-};
-
-}  // namespace
 
 extern "C" int skr_pearson_gemm_edges_needs_scratch(skr_ctx* ctx, const skr_operand* a, const skr_operand* b, int* needs) {
     SKR_REQUIRE(ctx && a && b && needs, "NULL argument");

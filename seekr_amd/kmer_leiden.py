@@ -86,16 +86,28 @@ def kmer_leiden(inputfile, mean, std, k, algo="RBERVertexPartition", rs=1.0, pea
     density=d (the other keyword `options` takes; default None): instead of a pearsoncutoff known in advance, keep the
     fraction d of the pairs — the cutoff is distribution.density_cutoff on the operand already filled (ties with the
     cutoff are kept, so at least floor(d N (N - 1) / 2) edges as long as the cutoff is positive); together with a
-    non-zero pearsoncutoff it raises ValueError."""
+    non-zero pearsoncutoff it raises ValueError.
+    knn=K, knn_mode="union" | "mutual" (keywords `options` takes too; default None, "union"): the k-nearest-neighbour graph
+    replaces the thresholded one (reciprocal.knn_graph: at most N K edges, positive r only); pearsoncutoff and density
+    must then be at their defaults, else ValueError.  With knn=None nothing changes."""
     if plotname is not None:
         raise NotImplementedError("the network plot is not built here; pass csvfile= and plot the nodes and edges files (plotname={!r})".format(plotname))
     leiden.algo_code(algo)
     kmers_top = options.pop("kmers_top", None)
     density = options.pop("density", None)
+    knn = options.pop("knn", None)
+    knn_mode = options.pop("knn_mode", "union")
     if options:
         raise TypeError("kmer_leiden() got an unexpected keyword argument {!r}".format(sorted(options)[0]))
     if kmers_top is not None:
         kmers_top = _lib.check_topk_k(kmers_top, "kmers_top")
+    if knn is not None:
+        from seekr_amd import consumers
+        if density is not None or float(pearsoncutoff) != 0:
+            raise ValueError("give knn, or density / a non-zero pearsoncutoff, not both (knn={!r}, density={!r}, "
+                             "pearsoncutoff={!r})".format(knn, density, pearsoncutoff))
+        knn = _lib.check_topk_k(knn, "knn")
+        consumers.knn_mode(knn_mode)
     if density is not None:
         from seekr_amd import distribution
         if float(pearsoncutoff) != 0:
@@ -117,7 +129,7 @@ def kmer_leiden(inputfile, mean, std, k, algo="RBERVertexPartition", rs=1.0, pea
     try:
         if density is not None:
             pearsoncutoff = distribution.density_cutoff(z, density)
-        membership, _, info = leiden.pearson_communities(z, float(pearsoncutoff), algo=algo, rs=float(rs))
+        membership, _, info = leiden.pearson_communities(z, float(pearsoncutoff), algo=algo, rs=float(rs), knn=knn, knn_mode=knn_mode)
         groups = None
         if kmers_top is not None and csvfile:
             from seekr_amd import explain

@@ -138,16 +138,26 @@ def communities(rows, cols, vals, n_nodes, algo="RBERVertexPartition", rs=1.0, m
     return membership, q.value, info
 
 
-def pearson_communities(z, cutoff=0.0, algo="RBERVertexPartition", rs=1.0, max_levels=32, max_sweeps=64, **kw):
+def pearson_communities(z, cutoff=0.0, algo="RBERVertexPartition", rs=1.0, max_levels=32, max_sweeps=64, knn=None, knn_mode="union",
+                        **kw):
     """communities() of the thresholded self-comparison of the prepared operand `z` (seekr_amd._lib.Operand): edge
     {i, j} weighs r[i, j] where !(r < cutoff), r > 0 and i != j (kmer_leiden.py:94-96, 106-107).  r never stands whole:
     consumers.pearson_edges reduces it to the edge list stripe by stripe.  That function hands the list back in host
     memory (each stripe's edges are downloaded as they are found), so here the finished list is UPLOADED once for
     skr_leiden — it does not stay on the device between the two steps.  `kw`: stripe_rows, fuse of pearson_edges.
+    knn=K: the k-nearest-neighbour graph replaces the thresholded one (reciprocal.knn_graph: {u, v} is an edge when v is
+    among u's K nearest or — knn_mode "mutual": and — u among v's, and r > 0; at most N K edges); `cutoff` must then be
+    at its default, else ValueError, and `kw` is the sweep's stripe_rows, panel_rows.
     Returns (membership, quality, info) with info["n_edges"] added."""
     from seekr_amd import consumers
     algo_code(algo)
-    rows, cols, vals = consumers.pearson_edges(z, cutoff, upper_only=True, **kw)
+    if knn is not None:
+        from seekr_amd import reciprocal
+        if float(cutoff) != 0:
+            raise ValueError("give knn or a non-zero cutoff, not both (knn={!r}, cutoff={!r})".format(knn, cutoff))
+        rows, cols, vals = reciprocal.knn_graph(z, knn, mode=knn_mode, **kw)
+    else:
+        rows, cols, vals = consumers.pearson_edges(z, cutoff, upper_only=True, **kw)
     keep = vals > 0  # a negative cutoff keeps negative cells and NaN passes the mask: neither is an edge weight
     if not keep.all():
         rows, cols, vals = rows[keep], cols[keep], vals[keep]

@@ -20,6 +20,8 @@ setup(
             "seekr_domain_pearson = seekr_amd.console_scripts:console_domain_pearson",
             # the k most correlated rows of every row, without the all-pairs matrix (no counterpart either)
             "seekr_nearest = seekr_amd.console_scripts:console_nearest",
+            # reciprocal nearest neighbours of two sets (or one) from one sweep (no counterpart either)
+            "seekr_reciprocal_hits = seekr_amd.console_scripts:console_reciprocal_hits",
             # the pairs with a corrected p-value <= alpha, without r, p or the corrected matrix (no counterpart either)
             "seekr_significant_pairs = seekr_amd.console_scripts:console_significant_pairs",
             # the windows of a target each query is significantly similar to (no counterpart either)
