@@ -470,6 +470,20 @@ int skr_gather_index(skr_ctx* ctx, const skr_mat* src, const skr_mat* index, int
 int skr_select_cells_ge(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t col_begin, int64_t col_end,
                         int64_t row_global0, int64_t col_global0, float cutoff, skr_mat* out_rows, skr_mat* out_cols,
                         skr_mat* out_vals, int64_t out_offset, int64_t* count, int* saw_nan);
+/* The cells of the float32 block r[0:nrows, col_begin:col_end] that a list names, gathered on the device.  rows / cols
+ * (SKR_U32) and out (SKR_F32) are vectors of S cells each; a listed cell is (rows[s], cols[s]) in GLOBAL indices, and
+ * the block's cell (i, j) — j r's own column index — is global (row_global0 + i, col_global0 + j), as for
+ * skr_select_cells_ge.  For s in [first, first + count): if the listed cell lies in the block, out[s] receives its 32
+ * bits unchanged (NaN payloads, -0 and denormals included); otherwise out[s] is not written.  Slots outside
+ * [first, first + count) are never written.  The origin is subtracted in 64 bits: global indices up to 2^32 - 1 never
+ * wrap into the block.  Duplicates are legal, every slot is served.  *gathered (may be NULL: the call then does not
+ * wait for the device) receives the number of slots written.  count == 0: SKR_OK, *gathered = 0, no launch.  Wrong
+ * dtypes, vectors of different lengths, first + count > S, negative arguments or a block range outside r:
+ * SKR_ERR_INVALID, nothing written.  One thread per slot in 256-thread workgroups, grid-stride; the count is one
+ * ballot per wave and step and one atomic per wave.  The same input gives the same bytes. */
+int skr_gather_cells(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t col_begin, int64_t col_end,
+                     int64_t row_global0, int64_t col_global0, const skr_mat* rows, const skr_mat* cols, int64_t first,
+                     int64_t count, skr_mat* out, int64_t* gathered);
 /* dst[dst_off + i] = src[src_off + i] for i < count, on the ctx's stream: two device vectors of the same dtype (SKR_U32,
  * SKR_F32 or SKR_F64), cells counted row-major.  A range outside either vector, or overlapping ranges of one
  * allocation: SKR_ERR_INVALID.                                                                                     */

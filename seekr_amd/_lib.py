@@ -126,6 +126,7 @@ SIGNATURES = {
     "skr_select_cells_ge": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, C.c_float, _p, _p, _p, _i64, C.POINTER(_i64),
                                   C.POINTER(_int)]),
     "skr_vec_copy": (_int, [_p, _p, _i64, _p, _i64, _i64]),
+    "skr_gather_cells": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _p, _p, _i64, _i64, _p, C.POINTER(_i64)]),
     "skr_run_pieces_ge": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, C.c_float, _p, _i64, _p, _p, _p, _p, _p, _p, _i64,
                                 C.POINTER(_i64), C.POINTER(_int)]),
     "skr_hist_key_digits": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _p, _int, _p, _p]),

@@ -5,8 +5,9 @@ counterpart in the reference), `seekr_nearest` (the k most correlated rows of ev
 `seekr_kmer_leiden` with the reference's flags (console_scripts.py:1033-1101) plus --edges, --kmers_top and --density, and
 `seekr_pair_kmers` (the k-mers behind the similarity of listed pairs: no counterpart) and `seekr_r_distribution` (the
 histogram, quantiles and density cutoffs of r without the matrix: likewise), and `seekr_domain_significant` and
-`seekr_domain_hits` (the significant windows of a target, and hot windows merged into intervals: likewise).  Only the commands on the hot path are
-provided."""
+`seekr_domain_hits` (the significant windows of a target, and hot windows merged into intervals: likewise), and
+`seekr_find_dist` and `seekr_find_pval` with the reference's flags (console_scripts.py:741-885).  Only the commands on
+the hot path are provided."""
 import argparse
 import sys
 
@@ -728,3 +729,81 @@ def console_r_distribution():
     _run_r_distribution(args.counts, args.counts2, args.binary_input, None if args.bins is None else int(args.bins),
                         None if args.range is None else (float(args.range[0]), float(args.range[1])), args.quantiles,
                         args.density, args.outfile)
+
+
+FIND_DIST_DOC = """
+Description
+-----------
+The background distribution of Pearson correlations: counts the k-mers of a background FASTA file on an MI355X,
+draws --subset_size of the pairwise correlations of its sequences without building the all-pairs matrix, and either
+writes that sample (default) or fits scipy distributions to it on the host (-fm) and writes the fits, best first.
+bkg_mean_<k>mers.npy and bkg_std_<k>mers.npy are written to the working directory: seekr_find_pval takes them.  Flags
+are those of the reference command of the same name; -pf draws no plot here, and 'default' as the FASTA file is refused
+(the default background is not shipped).
+
+Examples
+--------
+    100 000 sampled correlations:          seekr_find_dist background.fa -k 4 -sbt -sbs 100000 -o bkg_sample
+    the ten common models, ranked by KS:   seekr_find_dist background.fa -k 4 -sbt -fm -o bkg_fits
+    three models, ranked by AIC:           seekr_find_dist background.fa -mdl norm,gamma,lognorm -sbt -fm -statm aic -o bkg_fits
+"""
+
+FIND_PVAL_DOC = """
+Description
+-----------
+p-values of the Pearson correlations between the sequences of two FASTA files on an MI355X, against the output of
+seekr_find_dist: a CSV of fitted distributions (-ft distribution: the -bf-th is used; the ten common models have a
+device cdf) or a CSV of sampled correlations (-ft npy).  The result is a labelled CSV, rows the headers of the first
+file, columns those of the second.  Flags are those of the reference command of the same name.
+
+Examples
+--------
+    against the best fit:      seekr_find_pval a.fa b.fa bkg_mean_4mers.npy bkg_std_4mers.npy 4 bkg_fits.csv -o pvals
+    against the sample itself: seekr_find_pval a.fa b.fa bkg_mean_4mers.npy bkg_std_4mers.npy 4 bkg_sample.csv -ft npy -o pvals
+"""
+
+
+def console_find_dist():
+    from seekr_amd import find_dist
+    parser = argparse.ArgumentParser(usage=FIND_DIST_DOC, formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    parser.add_argument("fasta", help="full path of the FASTA file of background sequences.")
+    parser.add_argument("-k", "--kmer", default=4, help="length of the k-mers.")
+    parser.add_argument("-l", "--log2", default="Log2.post", choices=_LOG2, help="if and when the counts are log transformed.")
+    parser.add_argument("-mdl", "--models", default="common10",
+                        help="the models to fit: 'common10', 'all', or scipy.stats names separated by commas.")
+    parser.add_argument("-sbt", "--subsetting", action="store_true", help="use a random subset of the correlations.")
+    parser.add_argument("-sbs", "--subset_size", default=100000, help="size of that subset.")
+    parser.add_argument("-fm", "--fit_model", action="store_true", help="fit --models to the sample (needs scipy).")
+    parser.add_argument("-statm", "--statsmethod", default="ks", choices=["ks", "mse", "aic", "bic"],
+                        help="how the goodness of a fit is measured; smaller is better.")
+    parser.add_argument("-pb", "--progress_bar", action="store_true", help="show a progress bar over the models.")
+    parser.add_argument("-pf", "--plotfit", default=None, help="accepted for compatibility: no plot is drawn.")
+    parser.add_argument("-o", "--outputname", default=None, help="where the CSV goes; .csv is appended.  Omitted: nothing is saved.")
+    args = _parse_args_or_exit(parser)
+    models = args.models if args.models in ("common10", "all") else args.models.split(",")
+    find_dist.find_dist(args.fasta, int(args.kmer), args.log2, models, args.subsetting, int(args.subset_size), args.fit_model,
+                        args.statsmethod, args.progress_bar, args.plotfit, args.outputname)
+
+
+def console_find_pval():
+    from seekr_amd import find_dist, find_pval
+    parser = argparse.ArgumentParser(usage=FIND_PVAL_DOC, formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    parser.add_argument("seq1file", help="full path of the FASTA file whose sequences label the rows.")
+    parser.add_argument("seq2file", help="full path of the FASTA file whose sequences label the columns (may be the same file).")
+    parser.add_argument("mean_path", help="full path to the normalization mean vector numpy file.")
+    parser.add_argument("std_path", help="full path to the normalization std vector numpy file.")
+    parser.add_argument("kmer", help="length of the k-mers, consistent with the mean and std vector files.")
+    parser.add_argument("fitres_file", help="the CSV file seekr_find_dist wrote: fitted distributions or sampled correlations.")
+    parser.add_argument("-ft", "--fitres_type", default="distribution", choices=["distribution", "npy"],
+                        help="what fitres_file holds.")
+    parser.add_argument("-l", "--log2", default="Log2.post", choices=_LOG2, help="if and when the counts are log transformed.")
+    parser.add_argument("-bf", "--bestfit", default=1, help="which of the fitted distributions to use, counted from 1.")
+    parser.add_argument("-o", "--outputname", default=None, help="where the CSV goes; .csv is appended.  Omitted: nothing is saved.")
+    parser.add_argument("-pb", "--progress_bar", action="store_true", help="accepted for compatibility: there is no loop to show.")
+    args = _parse_args_or_exit(parser)
+    if args.fitres_type == "distribution":
+        fitres = find_dist.read_fit_csv(args.fitres_file)
+    else:
+        fitres = np.loadtxt(args.fitres_file, delimiter=",")
+    find_pval.find_pval(args.seq1file, args.seq2file, args.mean_path, args.std_path, int(args.kmer), fitres, args.log2,
+                        int(args.bestfit), args.outputname, args.progress_bar)

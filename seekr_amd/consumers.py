@@ -61,6 +61,153 @@ def subsample(values, size, rng=None):
     return out
 
 
+TRIU_MAX_N = (1 << 31) - 1  # n (n - 1) / 2 and the row starts then fit int64 with room to spare
+
+
+def _triu_row_starts(n):
+    """int64 [n]: the rank of the first cell of row i of np.triu_indices(n, 1), i (2n - i - 1) / 2 (row n - 1 is empty
+    and starts at n_cells)."""
+    i = np.arange(n, dtype=np.int64)
+    return i * (2 * np.int64(n) - i - 1) // 2
+
+
+def _check_triu_n(n):
+    n = int(n)
+    if not 0 <= n <= TRIU_MAX_N:
+        raise ValueError("n must be in 0..{} (got {})".format(TRIU_MAX_N, n))
+    return n
+
+
+def triu_unrank(index, n):
+    """(i, j), int64: the cells of an n x n matrix at the positions `index` of np.triu_indices(n, 1): the row is the
+    last one that starts at or before the index, row i starting at i (2n - i - 1) / 2 — np.searchsorted on the table of
+    row starts, or, above 2^22 rows (the table would be 16 GiB at n = 2^31 - 1), the same search by bisection on starts
+    computed as they are needed.  All arithmetic is int64.  n <= 2^31 - 1 (ValueError), index in [0, n (n - 1) / 2)
+    (IndexError)."""
+    n = _check_triu_n(n)
+    index = np.asarray(index, dtype=np.int64)
+    cells = n * (n - 1) // 2
+    if index.size and (index.min() < 0 or index.max() >= cells):
+        raise IndexError("index out of range for the {} cells of the upper triangle of {} rows".format(cells, n))
+    if n <= (1 << 22):  # the table itself: the rightmost row that starts at or before the index
+        i = np.searchsorted(_triu_row_starts(n), index, side="right").astype(np.int64) - 1
+    else:  # the same search without the table: bisection on the row starts, evaluated in int64 as they are needed
+        lo, hi = np.zeros(index.shape, np.int64), np.full(index.shape, max(n - 2, 0), np.int64)  # the row lies in lo ... hi
+        for _ in range(max(1, int(n - 1).bit_length())):
+            mid = (lo + hi + 1) // 2
+            right = mid * (2 * np.int64(n) - mid - 1) // 2 <= index
+            lo, hi = np.where(right, mid, lo), np.where(right, hi, mid - 1)
+        i = lo
+    start = i * (2 * np.int64(n) - i - 1) // 2
+    return i, index - start + i + 1
+
+
+def triu_rank(i, j, n):
+    """int64: the position of the cells (i, j), i < j < n, in np.triu_indices(n, 1)."""
+    n = _check_triu_n(n)
+    i, j = np.asarray(i, dtype=np.int64), np.asarray(j, dtype=np.int64)
+    if i.size and not (np.all(0 <= i) and np.all(i < j) and np.all(j < n)):
+        raise IndexError("cells of the upper triangle have 0 <= i < j < n")
+    return i * (2 * np.int64(n) - i - 1) // 2 + (j - i - 1)
+
+
+LEGACY_DRAW_MAX_CELLS = 1 << 29  # above this the permutation the reference draws from is more than 4 GiB
+SAMPLE_MAX = 1 << 28             # samples of one pearson_sample: the lists cost 12 bytes each on the device
+
+
+def draw_index(n_cells, size, rng=None):
+    """int64 [size]: which of n_cells values np.random.choice(values, size, replace=False) picks, in its order.
+    rng=None, n_cells <= LEGACY_DRAW_MAX_CELLS: np.random.permutation(n_cells)[:size] from numpy's legacy global state —
+    exactly what that choice() consumes and yields, so np.random.seed governs the sample as it does in the reference
+    (find_dist.py:169).  rng=None above the limit: Generator.choice(n_cells, size, replace=False) of a default_rng seeded
+    from np.random.randint(0, 2**31 - 1, size=4) — np.random.seed still governs the result and memory is O(size), but
+    the draw is NOT the reference's (which cannot run there at all: it needs the permutation and the whole triangle).
+    rng: a np.random.Generator, used that way at any size."""
+    n_cells, size = int(n_cells), int(size)
+    if size < 0 or size > n_cells:
+        raise ValueError("cannot take {} of {} cells without replacement".format(size, n_cells))
+    if rng is None:
+        if n_cells <= LEGACY_DRAW_MAX_CELLS:
+            # a copy: a slice would keep the whole permutation (8 bytes per cell) alive as long as the index lives
+            return np.array(np.random.permutation(n_cells)[:size], dtype=np.int64)
+        rng = np.random.default_rng(np.random.randint(0, 2 ** 31 - 1, size=4))
+    return np.asarray(rng.choice(n_cells, size, replace=False), dtype=np.int64)
+
+
+def gather_cells(r, rows, cols, out, first=0, count=None, nrows=None, col_begin=0, col_end=None, row_global0=0,
+                 col_global0=0):
+    """out[s] = the bits of the cell (rows[s], cols[s]) — global indices, uint32 device vectors — for the slots s in
+    [first, first + count) whose cell lies in the device block r[0:nrows, col_begin:col_end]; every other slot of the
+    float32 device vector `out` is left alone (skr_gather_cells).  Returns the number of slots written."""
+    slots = rows.rows * rows.cols
+    gathered = C.c_int64(0)
+    _lib.check(_lib.lib().skr_gather_cells(*block_args(r, nrows, col_begin, col_end, row_global0, col_global0), rows._h,
+                                           cols._h, int(first), int(slots - first if count is None else count), out._h,
+                                           C.byref(gathered)))
+    return gathered.value
+
+
+def pearson_sample(a, b=None, index=(), stripe_rows=8192, panel_rows=None):
+    """float32 [len(index)]: the cells of r = a b^T / K at the linear indices `index`, in the order of `index`, gathered
+    out of the blocks of Sweep(a, b, stripe_rows, panel_rows) — the bits of the r that sweep makes; r never stands whole.
+    a, b: prepared operands (_lib.Operand).  b=None: the upper triangle of a against itself, indices in triu_unrank
+    order (np.triu_indices(n, 1)); else row-major i * b.rows + j.  Duplicates are served.
+
+    The indices are sorted by (row, column) — which is their own order — and unranked on the host, and the sorted rows,
+    columns and an output vector go to the device once (12 bytes per sample).  A block's visitor finds the samples of its rows by searchsorted on the
+    sorted rows and hands that slice to skr_gather_cells, which skips those of other panels; the numbers gathered must
+    add up to len(index) (RuntimeError otherwise: every sample is gathered exactly once).  One download, and the sort is
+    undone on the host.  An index outside the cells: numpy's IndexError before any device call; more than SAMPLE_MAX
+    samples: ValueError."""
+    index = np.asarray(index)
+    if index.ndim != 1:
+        raise ValueError("index must be one-dimensional")
+    if index.size and not np.issubdtype(index.dtype, np.integer):
+        raise IndexError("arrays used as indices must be of integer (or boolean) type")
+    index = index.astype(np.int64, copy=False)
+    if len(index) > SAMPLE_MAX:
+        raise ValueError("at most {} samples in one call (got {})".format(SAMPLE_MAX, len(index)))
+    n, m = a.rows, (a if b is None else b).rows
+    cells = n * (n - 1) // 2 if b is None else n * m
+    if len(index) == 0:
+        return np.empty(0, np.float32)
+    lo, hi = int(index.min()), int(index.max())
+    if lo < 0 or hi >= cells:
+        raise IndexError("index {} is out of bounds for axis 0 with size {}".format(lo if lo < 0 else hi, cells))
+    if max(n, m) > 0xFFFFFFFF:
+        raise ValueError("rows and columns are uint32 on the device")
+    # both linear orders grow with (row, column), so sorting the indices IS the lexsort by (row, column) — and sorted
+    # indices unrank several times faster (the search walks the row starts in order); equal indices are equal cells, so
+    # the sort need not be stable
+    order = np.argsort(index)
+    ranked = index[order]
+    rows_sorted, cols_sorted = triu_unrank(ranked, n) if b is None else np.divmod(ranked, np.int64(m))
+    ctx = a.ctx
+    total = 0
+    with contextlib.ExitStack() as held:  # the sweep's buffer and the three lists: freed however this ends
+        sweep = held.enter_context(Sweep(a, b, stripe_rows, panel_rows))
+        d_rows = ctx.from_numpy(rows_sorted.astype(np.uint32))
+        held.callback(d_rows.free)
+        d_cols = ctx.from_numpy(cols_sorted.astype(np.uint32))
+        held.callback(d_cols.free)
+        d_out = ctx.empty(1, len(index), np.float32)
+        held.callback(d_out.free)
+
+        def gather(buf, nrows, upper_only, **where):
+            nonlocal total
+            first, last = np.searchsorted(rows_sorted, [where["row_global0"], where["row_global0"] + nrows])
+            if last > first:
+                total += gather_cells(buf, d_rows, d_cols, d_out, int(first), int(last - first), nrows=nrows, **where)
+
+        sweep.run(gather)
+        if total != len(index):
+            raise RuntimeError("{} of {} samples were gathered: every sample is gathered exactly once".format(total, len(index)))
+        got = np.array(d_out.to_numpy()).reshape(-1)
+    out = np.empty(len(index), np.float32)
+    out[order] = got
+    return out
+
+
 def ceil_float32(values):
     """The smallest float32 >= each value (NaN stays NaN).  The reference compares `fitres > sim[i, j]` in the
     background's own precision.  For a float32 v, b > v exactly when ceil32(b) > v: no float32 lies strictly between b and

@@ -1,5 +1,6 @@
 // skr_select_cells_ge: the cells of a query x target block of r with !(v < cutoff) as a (row, column, value) list that
-// stays on the device, and skr_vec_copy, which such a list grows by.  skr_edges (consumers.hip) is the graph's rule — it
+// stays on the device, skr_vec_copy, which such a list grows by, and skr_gather_cells, the opposite direction: the
+// values of the cells a list names.  skr_edges (consumers.hip) is the graph's rule — it
 // drops v == 0 and the global diagonal and gives a workgroup to each row; here every cell is an ordinary test and the
 // work is tiled in both directions.
 //
@@ -88,6 +89,31 @@ __global__ __launch_bounds__(kCellBlock) void cells_fill_pass(CellArgs a, const 
     }
 }
 
+// skr_gather_cells: one thread per listed slot.  The subtraction of the block's origin is made in 64 bits, so a global
+// index far from the block can never alias into it; a slot whose cell lies in the block receives the cell's 32 bits as
+// an integer (no float operation touches a NaN payload, -0 or a denormal), every other slot is left alone.  The loop
+// bound is the same for every lane of a wave, so the ballot that counts the served slots sees whole waves.
+__global__ __launch_bounds__(256) void gather_cells_pass(const uint32_t* __restrict__ r, int64_t ld, int64_t nrows,
+                                                           int64_t col_begin, int64_t col_end, int64_t row_global0,
+                                                           int64_t col_global0, const uint32_t* __restrict__ rows,
+                                                           const uint32_t* __restrict__ cols, int64_t first, int64_t count,
+                                                           uint32_t* __restrict__ out, unsigned long long* __restrict__ gathered) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long served = 0;
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < count; base += (int64_t)gridDim.x * 256) {
+        const int64_t t = base + threadIdx.x;
+        bool hit = false;
+        if (t < count) {
+            const int64_t s = first + t;
+            const int64_t i = (int64_t)rows[s] - row_global0, j = (int64_t)cols[s] - col_global0;
+            hit = i >= 0 && i < nrows && j >= col_begin && j < col_end;
+            if (hit) out[s] = r[i * ld + j];
+        }
+        served += (unsigned long long)__popcll(__ballot(hit));
+    }
+    if (gathered && lane == 0 && served) atomicAdd(gathered, served);
+}
+
 }  // namespace
 
 extern "C" int skr_select_cells_ge(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t col_begin, int64_t col_end,
@@ -145,6 +171,49 @@ extern "C" int skr_select_cells_ge(skr_ctx* ctx, const skr_mat* r, int64_t nrows
     hipLaunchKernelGGL(cells_fill_pass, dim3(grid), dim3(kCellBlock), 0, ctx->stream, a, counts, (unsigned long long)out_offset,
                        (uint32_t*)out_rows->data, (uint32_t*)out_cols->data, (float*)out_vals->data);
     SKR_HIP(hipGetLastError());
+    return SKR_OK;
+}
+
+extern "C" int skr_gather_cells(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t col_begin, int64_t col_end,
+                                int64_t row_global0, int64_t col_global0, const skr_mat* rows, const skr_mat* cols,
+                                int64_t first, int64_t count, skr_mat* out, int64_t* gathered) {
+    SKR_REQUIRE(ctx && r && rows && cols && out, "NULL argument");
+    SKR_REQUIRE(r->ctx == ctx && rows->ctx == ctx && cols->ctx == ctx && out->ctx == ctx, "foreign ctx");
+    SKR_REQUIRE(r->dtype == SKR_F32 && rows->dtype == SKR_U32 && cols->dtype == SKR_U32 && out->dtype == SKR_F32,
+                "r and out are F32, rows and cols are U32");
+    const int64_t slots = rows->rows * rows->cols;
+    SKR_REQUIRE(cols->rows * cols->cols == slots && out->rows * out->cols == slots, "rows, cols and out must have one length");
+    SKR_REQUIRE(first >= 0 && count >= 0 && first <= slots && count <= slots - first, "first + count exceeds the list");
+    SKR_REQUIRE(nrows >= 0 && nrows <= r->rows, "nrows out of range");
+    SKR_REQUIRE(col_begin >= 0 && col_begin <= col_end && col_end <= r->cols, "column range out of the matrix");
+    // (compared without adding to the origin: an origin near INT64_MAX must be refused, not wrapped)
+    SKR_REQUIRE(row_global0 >= 0 && col_global0 >= 0 && row_global0 <= 0xffffffffLL - nrows &&
+                    col_global0 <= 0xffffffffLL - col_end, "global indices must fit 32 bits");
+    SKR_TRY(skr_activate(ctx));
+    if (gathered) *gathered = 0;
+    if (count == 0) return SKR_OK;
+    unsigned long long* d_n = nullptr;
+    if (gathered) {
+        void* ws = nullptr;
+        SKR_TRY(skr_ctx_workspace(ctx, 8, &ws));
+        d_n = (unsigned long long*)ws;
+        SKR_HIP(hipMemsetAsync(d_n, 0, 8, ctx->stream));
+    }
+    // at most one workgroup per CU: a sweep's block rarely holds more than a few thousand of the listed cells
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((count + 255) / 256, (int64_t)ctx->num_cu));
+    {
+        SkrProfScope prof(ctx, "gather_cells");
+        hipLaunchKernelGGL(gather_cells_pass, dim3(grid), dim3(256), 0, ctx->stream, (const uint32_t*)r->data, r->cols, nrows,
+                           col_begin, col_end, row_global0, col_global0, (const uint32_t*)rows->data,
+                           (const uint32_t*)cols->data, first, count, (uint32_t*)out->data, d_n);
+        SKR_HIP(hipGetLastError());
+    }
+    if (gathered) {
+        unsigned long long h_n = 0;
+        SKR_HIP(hipMemcpyAsync(&h_n, d_n, 8, hipMemcpyDeviceToHost, ctx->stream));
+        SKR_HIP(hipStreamSynchronize(ctx->stream));
+        *gathered = (int64_t)h_n;
+    }
     return SKR_OK;
 }
 

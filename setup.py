@@ -16,6 +16,8 @@ setup(
             "seekr_pearson = seekr_amd.console_scripts:console_pearson",
             "seekr_norm_vectors = seekr_amd.console_scripts:console_norm_vectors",
             "seekr_adj_pval = seekr_amd.console_scripts:console_adj_pval",
+            "seekr_find_dist = seekr_amd.console_scripts:console_find_dist",
+            "seekr_find_pval = seekr_amd.console_scripts:console_find_pval",
             # sliding windows of a target against queries (no counterpart in the reference)
             "seekr_domain_pearson = seekr_amd.console_scripts:console_domain_pearson",
             # the k most correlated rows of every row, without the all-pairs matrix (no counterpart either)
