@@ -19,7 +19,8 @@
 
 #include "cell_tile.hpp"
 #include "common.hpp"
-#include "radix.hpp"
+#include "count_scan.hpp"
+#include "device_flag.hpp"
 
 namespace {
 
@@ -80,8 +81,8 @@ __global__ __launch_bounds__(kCellBlock) void cells_fill_pass(CellArgs a, const 
 #pragma unroll
         for (int j = 0; j < kCellPer; j++)
             if (keep[j]) {
-                out_row[pos] = (uint32_t)(a.row_global0 + row);
-                out_col[pos] = (uint32_t)(a.col_global0 + c0 + j);
+                out_row[pos] = (uint32_t)(a.b.row_global0 + row);
+                out_col[pos] = (uint32_t)(a.b.col_global0 + c0 + j);
                 out_val[pos] = v[j];
                 pos++;
             }
@@ -93,11 +94,10 @@ __global__ __launch_bounds__(kCellBlock) void cells_fill_pass(CellArgs a, const 
 // index far from the block can never alias into it; a slot whose cell lies in the block receives the cell's 32 bits as
 // an integer (no float operation touches a NaN payload, -0 or a denormal), every other slot is left alone.  The loop
 // bound is the same for every lane of a wave, so the ballot that counts the served slots sees whole waves.
-__global__ __launch_bounds__(256) void gather_cells_pass(const uint32_t* __restrict__ r, int64_t ld, int64_t nrows,
-                                                           int64_t col_begin, int64_t col_end, int64_t row_global0,
-                                                           int64_t col_global0, const uint32_t* __restrict__ rows,
+__global__ __launch_bounds__(256) void gather_cells_pass(SkrBlock b, const uint32_t* __restrict__ rows,
                                                            const uint32_t* __restrict__ cols, int64_t first, int64_t count,
                                                            uint32_t* __restrict__ out, unsigned long long* __restrict__ gathered) {
+    const uint32_t* __restrict__ r = reinterpret_cast<const uint32_t*>(b.r);  // the cells' bits
     const int lane = threadIdx.x & 63;
     unsigned long long served = 0;
     for (int64_t base = (int64_t)blockIdx.x * 256; base < count; base += (int64_t)gridDim.x * 256) {
@@ -105,9 +105,9 @@ __global__ __launch_bounds__(256) void gather_cells_pass(const uint32_t* __restr
         bool hit = false;
         if (t < count) {
             const int64_t s = first + t;
-            const int64_t i = (int64_t)rows[s] - row_global0, j = (int64_t)cols[s] - col_global0;
-            hit = i >= 0 && i < nrows && j >= col_begin && j < col_end;
-            if (hit) out[s] = r[i * ld + j];
+            const int64_t i = (int64_t)rows[s] - b.row_global0, j = (int64_t)cols[s] - b.col_global0;
+            hit = i >= 0 && i < b.rows && j >= b.col_begin && j < b.col_end;
+            if (hit) out[s] = r[i * b.ld + j];
         }
         served += (unsigned long long)__popcll(__ballot(hit));
     }
@@ -119,56 +119,33 @@ __global__ __launch_bounds__(256) void gather_cells_pass(const uint32_t* __restr
 extern "C" int skr_select_cells_ge(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t col_begin, int64_t col_end,
                                    int64_t row_global0, int64_t col_global0, float cutoff, skr_mat* out_rows,
                                    skr_mat* out_cols, skr_mat* out_vals, int64_t out_offset, int64_t* count, int* saw_nan) {
-    SKR_REQUIRE(ctx && r && count && r->ctx == ctx && r->dtype == SKR_F32, "need a float32 matrix of this ctx and a count");
-    SKR_REQUIRE(nrows >= 0 && nrows <= r->rows, "nrows out of range");
-    SKR_REQUIRE(col_begin >= 0 && col_begin <= col_end && col_end <= r->cols, "column range out of the matrix");
-    SKR_REQUIRE(row_global0 >= 0 && col_global0 >= 0 && row_global0 + nrows <= 0xffffffffLL &&
-                    col_global0 + col_end <= 0xffffffffLL, "global indices must fit 32 bits");
-    const bool fill = out_rows || out_cols || out_vals;
+    SkrBlock b;
+    SKR_TRY(skr_block(ctx, r, nrows, col_begin, col_end, row_global0, col_global0, SKR_FIT_BOTH, &b));
+    SKR_REQUIRE(count, "count must not be NULL");
+    skr_mat* const outs[3] = {out_rows, out_cols, out_vals};
+    const int dtypes[3] = {SKR_U32, SKR_U32, SKR_F32};
+    bool fill = false;
     int64_t cap = 0;
-    if (fill) {
-        SKR_REQUIRE(out_rows && out_cols && out_vals, "pass all three outputs or none");
-        SKR_REQUIRE(out_rows->ctx == ctx && out_cols->ctx == ctx && out_vals->ctx == ctx, "foreign ctx");
-        SKR_REQUIRE(out_rows->dtype == SKR_U32 && out_cols->dtype == SKR_U32 && out_vals->dtype == SKR_F32,
-                    "outputs are U32, U32, F32");
-        SKR_REQUIRE(out_offset >= 0, "out_offset must not be negative");
-        cap = std::min(out_rows->rows * out_rows->cols, std::min(out_cols->rows * out_cols->cols, out_vals->rows * out_vals->cols));
-    }
+    SKR_TRY(skr_list_outputs(ctx, outs, dtypes, 3, "outputs are U32, U32, F32", &fill, &cap));
+    SKR_REQUIRE(!fill || out_offset >= 0, "out_offset must not be negative");
     SKR_TRY(skr_activate(ctx));
     *count = 0;
     if (saw_nan) *saw_nan = 0;
     if (nrows == 0 || col_begin == col_end) return SKR_OK;
-    CellArgs a{(const float*)r->data, r->cols, nrows, col_begin, col_end, row_global0, col_global0, 0, 0, cutoff};
-    a.nseg = (col_end - col_begin + (kCellPer - 1) + kCellSegment - 1) / kCellSegment;
-    a.tiles = nrows * a.nseg;
-    void* ws = nullptr;
-    // per-tile counts and a zero behind them: scanned in place, offsets[tiles] is the total.  Then the scan's scratch and
-    // the NaN flag.
-    const size_t scan_words = skr_radix::scan_scratch_words(a.tiles + 1);
-    SKR_TRY(skr_ctx_workspace(ctx, ((size_t)a.tiles + 1 + scan_words + 1) * 8, &ws));
-    unsigned long long* counts = (unsigned long long*)ws;
-    unsigned long long* total = counts + a.tiles;
-    unsigned* nan_flag = (unsigned*)(total + 1 + scan_words);
-    SKR_HIP(hipMemsetAsync(total, 0, 8, ctx->stream));
-    SKR_HIP(hipMemsetAsync(nan_flag, 0, 8, ctx->stream));
+    const CellArgs a = cell_tiles(b, cutoff);
+    SkrCountScan<unsigned long long> cs;  // one count per tile, and the NaN flag
+    SKR_TRY(cs.begin(ctx, a.tiles, true));
     const unsigned grid = (unsigned)std::min<int64_t>(a.tiles, (int64_t)ctx->num_cu * 16);
     {
         SkrProfScope prof(ctx, "cells_count");
-        hipLaunchKernelGGL(cells_count_pass, dim3(grid), dim3(kCellBlock), 0, ctx->stream, a, counts, nan_flag);
+        hipLaunchKernelGGL(cells_count_pass, dim3(grid), dim3(kCellBlock), 0, ctx->stream, a, cs.counts, cs.flag);
         SKR_HIP(hipGetLastError());
     }
-    SKR_TRY(skr_radix::exclusive_scan<unsigned long long>(ctx, counts, a.tiles + 1, total + 1));
-    unsigned long long h_total = 0;
-    unsigned h_nan = 0;
-    SKR_HIP(hipMemcpyAsync(&h_total, total, 8, hipMemcpyDeviceToHost, ctx->stream));
-    SKR_HIP(hipMemcpyAsync(&h_nan, nan_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
-    SKR_HIP(hipStreamSynchronize(ctx->stream));
-    *count = (int64_t)h_total;
-    if (saw_nan) *saw_nan = h_nan ? 1 : 0;
-    if (!fill || h_total == 0) return SKR_OK;
-    if (out_offset > cap || (int64_t)h_total > cap - out_offset) return SKR_OK;  // does not fit: the caller grows its buffers
+    SKR_TRY(cs.finish(ctx, count, saw_nan));
+    if (!fill || *count == 0) return SKR_OK;
+    if (!skr_list_fits(cap, out_offset, *count)) return SKR_OK;  // the caller grows its buffers
     SkrProfScope prof(ctx, "cells_fill");
-    hipLaunchKernelGGL(cells_fill_pass, dim3(grid), dim3(kCellBlock), 0, ctx->stream, a, counts, (unsigned long long)out_offset,
+    hipLaunchKernelGGL(cells_fill_pass, dim3(grid), dim3(kCellBlock), 0, ctx->stream, a, cs.counts, (unsigned long long)out_offset,
                        (uint32_t*)out_rows->data, (uint32_t*)out_cols->data, (float*)out_vals->data);
     SKR_HIP(hipGetLastError());
     return SKR_OK;
@@ -177,43 +154,30 @@ extern "C" int skr_select_cells_ge(skr_ctx* ctx, const skr_mat* r, int64_t nrows
 extern "C" int skr_gather_cells(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t col_begin, int64_t col_end,
                                 int64_t row_global0, int64_t col_global0, const skr_mat* rows, const skr_mat* cols,
                                 int64_t first, int64_t count, skr_mat* out, int64_t* gathered) {
-    SKR_REQUIRE(ctx && r && rows && cols && out, "NULL argument");
-    SKR_REQUIRE(r->ctx == ctx && rows->ctx == ctx && cols->ctx == ctx && out->ctx == ctx, "foreign ctx");
-    SKR_REQUIRE(r->dtype == SKR_F32 && rows->dtype == SKR_U32 && cols->dtype == SKR_U32 && out->dtype == SKR_F32,
-                "r and out are F32, rows and cols are U32");
+    SkrBlock b;  // the listed cells are uint32 pairs: a block past 32 bits could hold none of them
+    SKR_TRY(skr_block(ctx, r, nrows, col_begin, col_end, row_global0, col_global0, SKR_FIT_BOTH, &b));
+    SKR_REQUIRE(rows && cols && out, "NULL argument");
+    SKR_REQUIRE(rows->ctx == ctx && cols->ctx == ctx && out->ctx == ctx, "foreign ctx");
+    SKR_REQUIRE(rows->dtype == SKR_U32 && cols->dtype == SKR_U32 && out->dtype == SKR_F32, "out is F32, rows and cols are U32");
     const int64_t slots = rows->rows * rows->cols;
     SKR_REQUIRE(cols->rows * cols->cols == slots && out->rows * out->cols == slots, "rows, cols and out must have one length");
     SKR_REQUIRE(first >= 0 && count >= 0 && first <= slots && count <= slots - first, "first + count exceeds the list");
-    SKR_REQUIRE(nrows >= 0 && nrows <= r->rows, "nrows out of range");
-    SKR_REQUIRE(col_begin >= 0 && col_begin <= col_end && col_end <= r->cols, "column range out of the matrix");
-    // (compared without adding to the origin: an origin near INT64_MAX must be refused, not wrapped)
-    SKR_REQUIRE(row_global0 >= 0 && col_global0 >= 0 && row_global0 <= 0xffffffffLL - nrows &&
-                    col_global0 <= 0xffffffffLL - col_end, "global indices must fit 32 bits");
     SKR_TRY(skr_activate(ctx));
     if (gathered) *gathered = 0;
     if (count == 0) return SKR_OK;
-    unsigned long long* d_n = nullptr;
-    if (gathered) {
-        void* ws = nullptr;
-        SKR_TRY(skr_ctx_workspace(ctx, 8, &ws));
-        d_n = (unsigned long long*)ws;
-        SKR_HIP(hipMemsetAsync(d_n, 0, 8, ctx->stream));
-    }
+    SkrDeviceFlag<unsigned long long> served;  // a counter: the kernel adds to it
+    SKR_TRY(served.arm(ctx, gathered != nullptr));
     // at most one workgroup per CU: a sweep's block rarely holds more than a few thousand of the listed cells
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((count + 255) / 256, (int64_t)ctx->num_cu));
     {
         SkrProfScope prof(ctx, "gather_cells");
-        hipLaunchKernelGGL(gather_cells_pass, dim3(grid), dim3(256), 0, ctx->stream, (const uint32_t*)r->data, r->cols, nrows,
-                           col_begin, col_end, row_global0, col_global0, (const uint32_t*)rows->data,
-                           (const uint32_t*)cols->data, first, count, (uint32_t*)out->data, d_n);
+        hipLaunchKernelGGL(gather_cells_pass, dim3(grid), dim3(256), 0, ctx->stream, b, (const uint32_t*)rows->data,
+                           (const uint32_t*)cols->data, first, count, (uint32_t*)out->data, served.d);
         SKR_HIP(hipGetLastError());
     }
-    if (gathered) {
-        unsigned long long h_n = 0;
-        SKR_HIP(hipMemcpyAsync(&h_n, d_n, 8, hipMemcpyDeviceToHost, ctx->stream));
-        SKR_HIP(hipStreamSynchronize(ctx->stream));
-        *gathered = (int64_t)h_n;
-    }
+    unsigned long long h_n = 0;
+    SKR_TRY(served.read(ctx, &h_n));
+    if (gathered) *gathered = (int64_t)h_n;
     return SKR_OK;
 }
 

@@ -7,8 +7,10 @@
 #include <algorithm>
 #include <cstring>
 
+#include "block.hpp"
 #include "common.hpp"
-#include "radix.hpp"
+#include "count_scan.hpp"
+#include "device_flag.hpp"
 #include "topk_key.hpp"
 
 namespace {
@@ -87,8 +89,7 @@ __global__ __launch_bounds__(256) void empirical_p_kernel(const float* __restric
 // A cell survives `ld_sim[ld_sim < cutoff] = 0; np.fill_diagonal(ld_sim, 0)` as a non-zero iff
 // !(v < cutoff) (NaN stays), v != 0 and it is off the diagonal.  upper: keep column > row only.
 struct EdgeArgs {
-    const float* r;
-    int64_t ld, rows, col_begin, col_end, row_global0, col_global0;
+    SkrBlock b;
     float cutoff;
     int upper;
 };
@@ -100,11 +101,11 @@ __device__ __forceinline__ bool edge_kept(const EdgeArgs& a, int64_t grow, int64
 
 __global__ __launch_bounds__(256) void edges_count_kernel(EdgeArgs a, unsigned long long* __restrict__ counts) {
     __shared__ unsigned red[4];
-    for (int64_t i = blockIdx.x; i < a.rows; i += gridDim.x) {
-        const float* row = a.r + (size_t)i * a.ld;
-        const int64_t grow = a.row_global0 + i;
+    for (int64_t i = blockIdx.x; i < a.b.rows; i += gridDim.x) {
+        const float* row = a.b.r + (size_t)i * a.b.ld;
+        const int64_t grow = a.b.row_global0 + i;
         unsigned n = 0;
-        for (int64_t c = a.col_begin + threadIdx.x; c < a.col_end; c += 256) n += edge_kept(a, grow, a.col_global0 + c, row[c]);
+        for (int64_t c = a.b.col_begin + threadIdx.x; c < a.b.col_end; c += 256) n += edge_kept(a, grow, a.b.col_global0 + c, row[c]);
         for (int off = 32; off; off >>= 1) n += __shfl_down(n, off, 64);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = n;
         __syncthreads();
@@ -120,14 +121,14 @@ __global__ __launch_bounds__(256) void edges_fill_kernel(EdgeArgs a, const unsig
                                                          float* __restrict__ out_val) {
     __shared__ unsigned wave_n[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int64_t i = blockIdx.x; i < a.rows; i += gridDim.x) {
-        const float* row = a.r + (size_t)i * a.ld;
-        const int64_t grow = a.row_global0 + i;
+    for (int64_t i = blockIdx.x; i < a.b.rows; i += gridDim.x) {
+        const float* row = a.b.r + (size_t)i * a.b.ld;
+        const int64_t grow = a.b.row_global0 + i;
         unsigned long long base = offsets[i];
-        for (int64_t c0 = a.col_begin; c0 < a.col_end; c0 += 256) {
+        for (int64_t c0 = a.b.col_begin; c0 < a.b.col_end; c0 += 256) {
             const int64_t c = c0 + threadIdx.x;
-            const float v = c < a.col_end ? row[c] : 0.f;
-            const bool keep = c < a.col_end && edge_kept(a, grow, a.col_global0 + c, v);
+            const float v = c < a.b.col_end ? row[c] : 0.f;
+            const bool keep = c < a.b.col_end && edge_kept(a, grow, a.b.col_global0 + c, v);
             const unsigned long long mask = __ballot(keep);
             if (lane == 0) wave_n[wave] = (unsigned)__popcll(mask);
             __syncthreads();
@@ -140,7 +141,7 @@ __global__ __launch_bounds__(256) void edges_fill_kernel(EdgeArgs a, const unsig
             if (keep) {
                 const unsigned long long pos = base + before + __popcll(mask & ((1ull << lane) - 1));
                 out_row[pos] = (uint32_t)grow;
-                out_col[pos] = (uint32_t)(a.col_global0 + c);
+                out_col[pos] = (uint32_t)(a.b.col_global0 + c);
                 out_val[pos] = v;
             }
             base += all;
@@ -153,6 +154,8 @@ __global__ __launch_bounds__(256) void edges_fill_kernel(EdgeArgs a, const unsig
 // smaller column — np.argsort(-row, kind="stable")[:k] with NaN last and the row's own (global)
 // diagonal cell excluded.  One workgroup per row; k selection passes over the row (it stays in the
 // L2): pass t finds the largest key below the t-1-th winner.  Keys order (value desc, column asc).
+// (The block arrives as its seven fields, not as an SkrBlock: the argument list is part of the kernel's symbol, and the
+// committed counter summaries bench.py quotes belong to the library's present set of kernel symbols.)
 __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict__ r, int64_t ld, int64_t rows,
                                                         int64_t col_begin, int64_t col_end, int64_t row_global0,
                                                         int64_t col_global0, int k, uint32_t* __restrict__ out_idx,
@@ -437,45 +440,30 @@ extern "C" int skr_empirical_pvalues(skr_ctx* ctx, const skr_mat* r, const skr_m
 extern "C" int skr_edges(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t col_begin, int64_t col_end,
                          int64_t row_global0, int64_t col_global0, float cutoff, int upper_only, skr_mat* out_rows,
                          skr_mat* out_cols, skr_mat* out_vals, int64_t* count) {
-    SKR_REQUIRE(ctx && r && count && r->ctx == ctx && r->dtype == SKR_F32, "need a float32 matrix of this ctx and a count");
-    SKR_REQUIRE(nrows >= 0 && nrows <= r->rows, "nrows out of range");
-    SKR_REQUIRE(col_begin >= 0 && col_begin <= col_end && col_end <= r->cols, "column range out of the matrix");
-    SKR_REQUIRE(row_global0 >= 0 && col_global0 >= 0 && row_global0 + nrows <= 0xffffffffLL &&
-                    col_global0 + col_end <= 0xffffffffLL, "global indices must fit 32 bits");
-    const bool fill = out_rows || out_cols || out_vals;
-    if (fill) {
-        SKR_REQUIRE(out_rows && out_cols && out_vals, "pass all three outputs or none");
-        SKR_REQUIRE(out_rows->ctx == ctx && out_cols->ctx == ctx && out_vals->ctx == ctx, "foreign ctx");
-        SKR_REQUIRE(out_rows->dtype == SKR_U32 && out_cols->dtype == SKR_U32 && out_vals->dtype == SKR_F32,
-                    "outputs are U32, U32, F32");
-    }
+    EdgeArgs a{{}, cutoff, upper_only != 0};
+    SKR_TRY(skr_block(ctx, r, nrows, col_begin, col_end, row_global0, col_global0, SKR_FIT_BOTH, &a.b));
+    SKR_REQUIRE(count, "count must not be NULL");
+    skr_mat* const outs[3] = {out_rows, out_cols, out_vals};
+    const int dtypes[3] = {SKR_U32, SKR_U32, SKR_F32};
+    bool fill = false;
+    int64_t cap = 0;
+    SKR_TRY(skr_list_outputs(ctx, outs, dtypes, 3, "outputs are U32, U32, F32", &fill, &cap));
     SKR_TRY(skr_activate(ctx));
     *count = 0;
     if (nrows == 0 || col_begin == col_end) return SKR_OK;
-    void* ws = nullptr;
-    // per-row counts and a zero behind them: scanned in place, offsets[nrows] is the total.  Then the scan's scratch.
-    SKR_TRY(skr_ctx_workspace(ctx, ((size_t)nrows + 1 + skr_radix::scan_scratch_words(nrows + 1)) * 8, &ws));
-    unsigned long long* counts = (unsigned long long*)ws;
-    unsigned long long* total = counts + nrows;
-    SKR_HIP(hipMemsetAsync(total, 0, 8, ctx->stream));
-    EdgeArgs a{(const float*)r->data, r->cols, nrows, col_begin, col_end, row_global0, col_global0, cutoff, upper_only != 0};
+    SkrCountScan<unsigned long long> cs;  // one count per row
+    SKR_TRY(cs.begin(ctx, nrows));
     const unsigned grid = (unsigned)std::min<int64_t>(nrows, (int64_t)ctx->num_cu * 16);
     {
         SkrProfScope prof(ctx, "edges_count");
-        hipLaunchKernelGGL(edges_count_kernel, dim3(grid), dim3(256), 0, ctx->stream, a, counts);
+        hipLaunchKernelGGL(edges_count_kernel, dim3(grid), dim3(256), 0, ctx->stream, a, cs.counts);
         SKR_HIP(hipGetLastError());
     }
-    SKR_TRY(skr_radix::exclusive_scan<unsigned long long>(ctx, counts, nrows + 1, total + 1));
-    unsigned long long h_total = 0;
-    SKR_HIP(hipMemcpyAsync(&h_total, total, 8, hipMemcpyDeviceToHost, ctx->stream));
-    SKR_HIP(hipStreamSynchronize(ctx->stream));
-    *count = (int64_t)h_total;
-    if (!fill || h_total == 0) return SKR_OK;
-    const int64_t cap = std::min(out_rows->rows * out_rows->cols, std::min(out_cols->rows * out_cols->cols,
-                                                                           out_vals->rows * out_vals->cols));
-    SKR_REQUIRE((int64_t)h_total <= cap, "%lld edges do not fit outputs of %lld cells", (long long)h_total, (long long)cap);
+    SKR_TRY(cs.finish(ctx, count));
+    if (!fill || *count == 0) return SKR_OK;
+    SKR_REQUIRE(*count <= cap, "%lld edges do not fit outputs of %lld cells", (long long)*count, (long long)cap);
     SkrProfScope prof(ctx, "edges_fill");
-    hipLaunchKernelGGL(edges_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream, a, counts, (uint32_t*)out_rows->data,
+    hipLaunchKernelGGL(edges_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream, a, cs.counts, (uint32_t*)out_rows->data,
                        (uint32_t*)out_cols->data, (float*)out_vals->data);
     SKR_HIP(hipGetLastError());
     return SKR_OK;
@@ -491,12 +479,9 @@ extern "C" int skr_select_le(skr_ctx* ctx, const skr_mat* values, double bound, 
     *count = 0;
     if (n == 0) return SKR_OK;
     const int64_t tiles = (n + kSelectTile - 1) / kSelectTile;
-    void* ws = nullptr;
-    // per-tile counts and a zero behind them: scanned in place, offsets[tiles] is the total.  Then the scan's scratch.
-    SKR_TRY(skr_ctx_workspace(ctx, ((size_t)tiles + 1 + skr_radix::scan_scratch_words(tiles + 1)) * 8, &ws));
-    unsigned long long* counts = (unsigned long long*)ws;
-    unsigned long long* total = counts + tiles;
-    SKR_HIP(hipMemsetAsync(total, 0, 8, ctx->stream));
+    SkrCountScan<unsigned long long> cs;  // one count per tile
+    SKR_TRY(cs.begin(ctx, tiles));
+    unsigned long long* counts = cs.counts;
     const dim3 grid((unsigned)std::min<int64_t>(tiles, (int64_t)ctx->num_cu * 16));
     const bool f64 = values->dtype == SKR_F64;
     {
@@ -509,14 +494,10 @@ extern "C" int skr_select_le(skr_ctx* ctx, const skr_mat* values, double bound, 
                                bound, tiles, counts);
         SKR_HIP(hipGetLastError());
     }
-    SKR_TRY(skr_radix::exclusive_scan<unsigned long long>(ctx, counts, tiles + 1, total + 1));
-    unsigned long long h_total = 0;
-    SKR_HIP(hipMemcpyAsync(&h_total, total, 8, hipMemcpyDeviceToHost, ctx->stream));
-    SKR_HIP(hipStreamSynchronize(ctx->stream));
-    *count = (int64_t)h_total;
-    if (!out_index || h_total == 0) return SKR_OK;
+    SKR_TRY(cs.finish(ctx, count));
+    if (!out_index || *count == 0) return SKR_OK;
     const int64_t cap = out_index->rows * out_index->cols;
-    SKR_REQUIRE((int64_t)h_total <= cap, "%lld positions do not fit an output of %lld cells", (long long)h_total, (long long)cap);
+    SKR_REQUIRE(*count <= cap, "%lld positions do not fit an output of %lld cells", (long long)*count, (long long)cap);
     SkrProfScope prof(ctx, "select_fill");
     if (f64)
         hipLaunchKernelGGL(select_fill_kernel<double>, grid, dim3(kSelectTile), 0, ctx->stream, (const double*)values->data, n, bound,
@@ -537,45 +518,41 @@ extern "C" int skr_gather_index(skr_ctx* ctx, const skr_mat* src, const skr_mat*
     SKR_REQUIRE(out->data != src->data || count == 0, "out must not alias src");
     SKR_TRY(skr_activate(ctx));
     if (count == 0) return SKR_OK;
-    void* ws = nullptr;
-    SKR_TRY(skr_ctx_workspace(ctx, 64, &ws));
-    int* bad = (int*)ws;
-    SKR_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
+    SkrDeviceFlag<int> bad;
+    SKR_TRY(bad.arm(ctx));
     const int64_t n_src = src->rows * src->cols;
     {
         SkrProfScope prof(ctx, "gather_index");
         if (src->elem() == 8)
             hipLaunchKernelGGL(gather_index_kernel<unsigned long long>, dim3(skr_grid(ctx, count)), dim3(256), 0, ctx->stream,
                                (const unsigned long long*)src->data, n_src, (const uint32_t*)index->data, count,
-                               (unsigned long long*)out->data, bad);
+                               (unsigned long long*)out->data, bad.d);
         else
             hipLaunchKernelGGL(gather_index_kernel<uint32_t>, dim3(skr_grid(ctx, count)), dim3(256), 0, ctx->stream,
-                               (const uint32_t*)src->data, n_src, (const uint32_t*)index->data, count, (uint32_t*)out->data, bad);
+                               (const uint32_t*)src->data, n_src, (const uint32_t*)index->data, count, (uint32_t*)out->data, bad.d);
         SKR_HIP(hipGetLastError());
     }
     int h_bad = 0;
-    SKR_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SKR_HIP(hipStreamSynchronize(ctx->stream));
+    SKR_TRY(bad.read(ctx, &h_bad));
     SKR_REQUIRE(!h_bad, "an index lies outside the %lld cells of src", (long long)n_src);
     return SKR_OK;
 }
 
 extern "C" int skr_topk_rows(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t col_begin, int64_t col_end,
                              int64_t row_global0, int64_t col_global0, int k, skr_mat* out_idx, skr_mat* out_val) {
-    SKR_REQUIRE(ctx && r && out_idx && out_val, "NULL argument");
-    SKR_REQUIRE(r->ctx == ctx && out_idx->ctx == ctx && out_val->ctx == ctx, "foreign ctx");
-    SKR_REQUIRE(r->dtype == SKR_F32 && out_idx->dtype == SKR_U32 && out_val->dtype == SKR_F32, "r F32, out_idx U32, out_val F32");
-    SKR_REQUIRE(nrows >= 0 && nrows <= r->rows, "nrows out of range");
-    SKR_REQUIRE(col_begin >= 0 && col_begin <= col_end && col_end <= r->cols, "column range out of the matrix");
+    SkrBlock b;  // only columns are written; 0xFFFFFFFF is the index of an unfilled slot
+    SKR_TRY(skr_block(ctx, r, nrows, col_begin, col_end, row_global0, col_global0, SKR_FIT_COLS, &b));
+    SKR_REQUIRE(out_idx && out_val, "NULL argument");
+    SKR_REQUIRE(out_idx->ctx == ctx && out_val->ctx == ctx, "foreign ctx");
+    SKR_REQUIRE(out_idx->dtype == SKR_U32 && out_val->dtype == SKR_F32, "out_idx U32, out_val F32");
     SKR_REQUIRE(k >= 1 && k <= 4096, "k must be in 1..4096");
-    SKR_REQUIRE(row_global0 >= 0 && col_global0 >= 0 && col_global0 + col_end <= 0xffffffffLL, "global indices must fit 32 bits");
     SKR_REQUIRE(out_idx->rows * out_idx->cols >= nrows * k && out_val->rows * out_val->cols >= nrows * k,
                 "outputs must hold %lld cells", (long long)(nrows * k));
     SKR_TRY(skr_activate(ctx));
     if (nrows == 0) return SKR_OK;
     SkrProfScope prof(ctx, "topk_rows");
     hipLaunchKernelGGL(topk_rows_kernel, dim3((unsigned)std::min<int64_t>(nrows, (int64_t)ctx->num_cu * 16)), dim3(256), 0,
-                       ctx->stream, (const float*)r->data, r->cols, nrows, col_begin, col_end, row_global0, col_global0, k,
+                       ctx->stream, b.r, b.ld, b.rows, b.col_begin, b.col_end, b.row_global0, b.col_global0, k,
                        (uint32_t*)out_idx->data, (float*)out_val->data);
     SKR_HIP(hipGetLastError());
     return SKR_OK;
@@ -623,26 +600,20 @@ extern "C" int skr_parametric_pvalues(skr_ctx* ctx, const skr_mat* r, const char
     SKR_TRY(skr_activate(ctx));
     const int64_t cells = r->rows * r->cols;
     if (cells == 0) return SKR_OK;
-    if (d.dist == DIST_CHI2 || d.dist == DIST_GAMMA) {
-        void* ws = nullptr;
-        SKR_TRY(skr_ctx_workspace(ctx, 64, &ws));
-        d.not_converged = (int*)ws;
-        SKR_HIP(hipMemsetAsync(d.not_converged, 0, sizeof(int), ctx->stream));
-    }
+    SkrDeviceFlag<int> not_converged;  // only gamma_p's loops can raise it
+    SKR_TRY(not_converged.arm(ctx, d.dist == DIST_CHI2 || d.dist == DIST_GAMMA));  // (not a DIST_BAD_SHAPE)
+    d.not_converged = not_converged.d;
     {
         SkrProfScope prof(ctx, "parametric_pvalues");
         hipLaunchKernelGGL(parametric_p_kernel, dim3(skr_grid(ctx, cells)), dim3(256), 0, ctx->stream, (const float*)r->data,
                            cells, d, (float*)p->data);
         SKR_HIP(hipGetLastError());
     }
-    if (d.not_converged) {
-        int h_flag = 0;
-        SKR_HIP(hipMemcpyAsync(&h_flag, d.not_converged, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        SKR_HIP(hipStreamSynchronize(ctx->stream));
-        if (h_flag)
-            return skr_set_error(SKR_ERR_UNSUPPORTED,
-                                 "%s with shape %g: the incomplete gamma function did not converge within %d terms for some "
-                                 "cell; p holds no valid result", dist_name, d.shape, d.max_terms);
-    }
+    int h_flag = 0;
+    SKR_TRY(not_converged.read(ctx, &h_flag));
+    if (h_flag)
+        return skr_set_error(SKR_ERR_UNSUPPORTED,
+                             "%s with shape %g: the incomplete gamma function did not converge within %d terms for some "
+                             "cell; p holds no valid result", dist_name, d.shape, d.max_terms);
     return SKR_OK;
 }

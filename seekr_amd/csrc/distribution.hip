@@ -6,7 +6,8 @@
 // (col_global0 + j) is greater than their global row (row_global0 + i) — skr_edges' rule.  There is no zero rule.
 // NaN rule: a NaN cell of either sign bit goes into a counter of its own and into no bin.
 //
-// Key digits: key(v) is the uint32 whose order is the order of the float32 values, -0 just below +0 (significant._key).
+// Key digits: key(v) is float_key.hpp's uint32, whose order is the order of the float32 values, -0 just below +0
+// (significant._key).
 // A cell whose top prefix_bits key bits equal prefixes[q] adds one to hist[q][(key >> shift) & (2^bits - 1)]; with
 // prefix_bits = 0 there is one histogram of every cell.  A radix descent over the key (distribution.py) is three such
 // passes.  Edge table: bin b holds edges[b] <= v < edges[b + 1], the last bin is closed on the right, and the cells
@@ -27,6 +28,7 @@
 
 #include "cell_tile.hpp"
 #include "common.hpp"
+#include "float_key.hpp"
 
 namespace {
 
@@ -42,11 +44,6 @@ struct DistArgs {
     int n_edges;                               // edge table
     int total_bins;                            // counters behind one another: the bins, then below, above (edge table), nan
 };
-
-__device__ __forceinline__ uint32_t dist_key(float v) {
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // the counter of one cell: -1 for a cell that is not counted
 template <bool kEdges>
@@ -67,7 +64,7 @@ __device__ __forceinline__ int dist_bin(const DistArgs& d, const float* edges, f
         }
         return lo;
     } else {
-        const uint32_t key = dist_key(v);
+        const uint32_t key = skr_float_key(v);
         const uint32_t top = d.prefix_bits ? key >> (32 - d.prefix_bits) : 0u;
         const int digit = (int)((key >> d.shift) & ((1u << d.bits) - 1u));
         int q = -1;
@@ -117,7 +114,7 @@ __global__ __launch_bounds__(kCellBlock) void dist_hist_pass(CellArgs a, DistArg
             if (h == 1 && !second) break;
 #pragma unroll
             for (int j = 0; j < kCellPer; j++) {
-                const bool counted = live[h][j] && (!d.upper_only || a.col_global0 + c0[h] + j > a.row_global0 + row[h]);
+                const bool counted = live[h][j] && (!d.upper_only || a.b.col_global0 + c0[h] + j > a.b.row_global0 + row[h]);
                 dist_add<kMatch>(hist, dist_bin<kEdges>(d, edges, v[h][j], counted));
             }
         }
@@ -127,19 +124,6 @@ __global__ __launch_bounds__(kCellBlock) void dist_hist_pass(CellArgs a, DistArg
         const unsigned n = hist[i];
         if (n) atomicAdd(&g_counts[i], (unsigned long long)n);
     }
-}
-
-// the checks both entry points share, and the tiling
-int dist_block(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t col_begin, int64_t col_end, int64_t row_global0,
-               int64_t col_global0, CellArgs* a) {
-    SKR_REQUIRE(ctx && r && r->ctx == ctx && r->dtype == SKR_F32, "need a float32 matrix of this ctx");
-    SKR_REQUIRE(nrows >= 0 && nrows <= r->rows, "nrows out of range");
-    SKR_REQUIRE(col_begin >= 0 && col_begin <= col_end && col_end <= r->cols, "column range out of the matrix");
-    SKR_REQUIRE(row_global0 >= 0 && col_global0 >= 0, "global indices must not be negative");
-    *a = CellArgs{(const float*)r->data, r->cols, nrows, col_begin, col_end, row_global0, col_global0, 0, 0, 0.f};
-    a->nseg = (col_end - col_begin + (kCellPer - 1) + kCellSegment - 1) / kCellSegment;
-    a->tiles = nrows * a->nseg;
-    return SKR_OK;
 }
 
 // zero the counters, run the pass, download: out[0 : total_bins] receives this block's counts
@@ -183,8 +167,8 @@ int dist_run(skr_ctx* ctx, const CellArgs& a, const DistArgs& d, const float* h_
 extern "C" int skr_hist_key_digits(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t col_begin, int64_t col_end,
                                    int64_t row_global0, int64_t col_global0, int upper_only, int shift, int bits,
                                    int prefix_bits, const uint32_t* prefixes, int n_prefixes, uint64_t* hist, uint64_t* nan) {
-    CellArgs a;
-    SKR_TRY(dist_block(ctx, r, nrows, col_begin, col_end, row_global0, col_global0, &a));
+    SkrBlock b;  // counts only: no global index is written
+    SKR_TRY(skr_block(ctx, r, nrows, col_begin, col_end, row_global0, col_global0, SKR_FIT_NONE, &b));
     SKR_REQUIRE(hist && nan, "hist and nan must not be NULL");
     SKR_REQUIRE(bits >= 1 && bits <= 12 && shift >= 0 && shift + bits <= 32, "need 1 <= bits <= 12 and shift + bits <= 32");
     SKR_REQUIRE(prefix_bits >= 0 && prefix_bits <= 32, "prefix_bits out of range");
@@ -201,7 +185,7 @@ extern "C" int skr_hist_key_digits(skr_ctx* ctx, const skr_mat* r, int64_t nrows
     }
     d.total_bins = (n_prefixes << bits) + 1;
     std::vector<unsigned long long> got;
-    SKR_TRY(dist_run(ctx, a, d, nullptr, &got));
+    SKR_TRY(dist_run(ctx, cell_tiles(b, 0.f), d, nullptr, &got));
     for (int i = 0; i < d.total_bins - 1; i++) hist[i] += got[(size_t)i];
     *nan += got[(size_t)d.total_bins - 1];
     return SKR_OK;
@@ -210,8 +194,8 @@ extern "C" int skr_hist_key_digits(skr_ctx* ctx, const skr_mat* r, int64_t nrows
 extern "C" int skr_hist_edges(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t col_begin, int64_t col_end,
                               int64_t row_global0, int64_t col_global0, int upper_only, const float* edges, int n_edges,
                               uint64_t* hist, uint64_t* below, uint64_t* above, uint64_t* nan) {
-    CellArgs a;
-    SKR_TRY(dist_block(ctx, r, nrows, col_begin, col_end, row_global0, col_global0, &a));
+    SkrBlock b;  // counts only: no global index is written
+    SKR_TRY(skr_block(ctx, r, nrows, col_begin, col_end, row_global0, col_global0, SKR_FIT_NONE, &b));
     SKR_REQUIRE(hist && below && above && nan, "hist, below, above and nan must not be NULL");
     SKR_REQUIRE(edges && n_edges >= 2 && n_edges <= kDistMaxEdges, "2 to %d edges", kDistMaxEdges);
     for (int i = 0; i < n_edges; i++) {
@@ -223,7 +207,7 @@ extern "C" int skr_hist_edges(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int
     d.n_edges = n_edges;
     d.total_bins = n_edges - 1 + 3;
     std::vector<unsigned long long> got;
-    SKR_TRY(dist_run(ctx, a, d, edges, &got));
+    SKR_TRY(dist_run(ctx, cell_tiles(b, 0.f), d, edges, &got));
     const int nb = n_edges - 1;
     for (int i = 0; i < nb; i++) hist[i] += got[(size_t)i];
     *below += got[(size_t)nb], *above += got[(size_t)nb + 1], *nan += got[(size_t)nb + 2];

@@ -18,14 +18,15 @@
 // slot in its tile is the number of starts before it (four ballots and the wave totals, as in cells_fill_pass: lanes in
 // order, cells in order within the lane), and every hot cell knows the slot of its own piece the same way.  The piece's
 // n_hot is an LDS atomicAdd, its last position an LDS atomicMax, its peak ONE 64-bit LDS atomicMax of
-// (key(v) << 32) | (0xFFFFFFFF - position): the largest value by the order of distribution.hip's key (-0 below +0) and the
+// (key(v) << 32) | (0xFFFFFFFF - position): the largest value by the order of float_key.hpp's key (-0 below +0) and the
 // earliest position that reaches it, whatever order the lanes arrive in.  Integers and maxima only: the same input gives
 // the same bytes on every run.  No global atomic per cell.
 #include <algorithm>
 
 #include "cell_tile.hpp"
 #include "common.hpp"
-#include "radix.hpp"
+#include "count_scan.hpp"
+#include "float_key.hpp"
 
 namespace {
 
@@ -36,15 +37,6 @@ struct RunArgs {
     int max_gap;          // clamped to kCellSegment: no gap inside a tile is longer
 };
 
-__device__ __forceinline__ uint32_t run_key(float v) {  // distribution.hip: dist_key
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float run_unkey(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
-
 // The lane's four cells of tile t: hot[j], and start[j] (the cell begins a piece).  One __syncthreads inside: every lane
 // of the workgroup calls it.  scan_tot: kRunWaves words of LDS.  nan: set when a live cell is NaN.
 __device__ __forceinline__ void find_starts(const CellArgs& a, const RunArgs& ra, int64_t t, unsigned* scan_tot,
@@ -54,9 +46,9 @@ __device__ __forceinline__ void find_starts(const CellArgs& a, const RunArgs& ra
     const unsigned p0 = threadIdx.x * kCellPer;
     bool live[kCellPer], bnd[kCellPer];
     load_group(a, t, v, live, row, c0);
-    const int64_t seg0 = c0 - (int64_t)p0, first_live = seg0 > a.col_begin ? seg0 : a.col_begin;  // (only the row's first segment starts below col_begin)
+    const int64_t seg0 = c0 - (int64_t)p0, first_live = seg0 > a.b.col_begin ? seg0 : a.b.col_begin;  // (only the row's first segment starts below col_begin)
     if (ra.seq) {
-        const uint32_t* sp = ra.seq + a.col_global0;  // by r's own column: the live ones lie in [col_begin, col_end)
+        const uint32_t* sp = ra.seq + a.b.col_global0;  // by r's own column: the live ones lie in [col_begin, col_end)
         uint32_t s[kCellPer];
         if (live[0] && live[kCellPer - 1] && (((uintptr_t)(sp + c0)) & 15) == 0) {  // a whole group, aligned in the vector too
             const uint4 q = *reinterpret_cast<const uint4*>(sp + c0);
@@ -179,20 +171,20 @@ __global__ __launch_bounds__(kCellBlock) void runs_fill_pass(CellArgs a, RunArgs
                 const unsigned pos = p0 + j;
                 atomicAdd(&p_nhot[id[j]], 1u);
                 atomicMax(&p_last[id[j]], pos);
-                atomicMax(&p_peak[id[j]], ((unsigned long long)run_key(v[j]) << 32) | (0xFFFFFFFFu - pos));
+                atomicMax(&p_peak[id[j]], ((unsigned long long)skr_float_key(v[j]) << 32) | (0xFFFFFFFFu - pos));
             }
         __syncthreads();
-        const int64_t g0 = a.col_global0 + c0 - (int64_t)p0;  // global column of position 0
+        const int64_t g0 = a.b.col_global0 + c0 - (int64_t)p0;  // global column of position 0
 #pragma unroll
         for (int j = 0; j < kCellPer; j++)
             if (start[j]) {
                 const unsigned long long at = out_offset + base + id[j];
                 const unsigned long long pk = p_peak[id[j]];
-                out.row[at] = (uint32_t)(a.row_global0 + row);
+                out.row[at] = (uint32_t)(a.b.row_global0 + row);
                 out.first[at] = (uint32_t)(g0 + p0 + j);
                 out.last[at] = (uint32_t)(g0 + p_last[id[j]]);
                 out.n_hot[at] = p_nhot[id[j]];
-                out.peak[at] = run_unkey((uint32_t)(pk >> 32));
+                out.peak[at] = skr_float_unkey((uint32_t)(pk >> 32));
                 out.peak_col[at] = (uint32_t)(g0 + (0xFFFFFFFFu - (uint32_t)pk));
             }
         // (the next tile writes these LDS cells only after two more barriers)
@@ -205,66 +197,41 @@ extern "C" int skr_run_pieces_ge(skr_ctx* ctx, const skr_mat* r, int64_t nrows, 
                                  int64_t row_global0, int64_t col_global0, float cutoff, const skr_mat* seq_of_col,
                                  int64_t max_gap, skr_mat* out_rows, skr_mat* out_first, skr_mat* out_last, skr_mat* out_nhot,
                                  skr_mat* out_peak, skr_mat* out_peak_col, int64_t out_offset, int64_t* count, int* saw_nan) {
-    SKR_REQUIRE(ctx && r && count && r->ctx == ctx && r->dtype == SKR_F32, "need a float32 matrix of this ctx and a count");
-    SKR_REQUIRE(nrows >= 0 && nrows <= r->rows, "nrows out of range");
-    SKR_REQUIRE(col_begin >= 0 && col_begin <= col_end && col_end <= r->cols, "column range out of the matrix");
-    SKR_REQUIRE(row_global0 >= 0 && col_global0 >= 0 && row_global0 + nrows <= 0xffffffffLL &&
-                    col_global0 + col_end <= 0xffffffffLL, "global indices must fit 32 bits");
+    SkrBlock b;
+    SKR_TRY(skr_block(ctx, r, nrows, col_begin, col_end, row_global0, col_global0, SKR_FIT_BOTH, &b));
+    SKR_REQUIRE(count, "count must not be NULL");
     SKR_REQUIRE(max_gap >= 0, "max_gap must not be negative");
     if (seq_of_col) {
         SKR_REQUIRE(seq_of_col->ctx == ctx && seq_of_col->dtype == SKR_U32, "seq_of_col is a U32 vector of this ctx");
         SKR_REQUIRE(seq_of_col->rows * seq_of_col->cols >= col_global0 + col_end, "seq_of_col must reach col_global0 + col_end");
     }
-    skr_mat* outs[6] = {out_rows, out_first, out_last, out_nhot, out_peak, out_peak_col};
-    const bool fill = std::any_of(outs, outs + 6, [](const skr_mat* m) { return m != nullptr; });
+    skr_mat* const outs[6] = {out_rows, out_first, out_last, out_nhot, out_peak, out_peak_col};
+    const int dtypes[6] = {SKR_U32, SKR_U32, SKR_U32, SKR_U32, SKR_F32, SKR_U32};
+    bool fill = false;
     int64_t cap = 0;
-    if (fill) {
-        cap = INT64_MAX;
-        for (int i = 0; i < 6; i++) {
-            SKR_REQUIRE(outs[i], "pass all six outputs or none");
-            SKR_REQUIRE(outs[i]->ctx == ctx, "foreign ctx");
-            SKR_REQUIRE(outs[i]->dtype == (i == 4 ? SKR_F32 : SKR_U32), "outputs are U32 except the peak, which is F32");
-            cap = std::min(cap, outs[i]->rows * outs[i]->cols);
-        }
-        SKR_REQUIRE(out_offset >= 0, "out_offset must not be negative");
-    }
+    SKR_TRY(skr_list_outputs(ctx, outs, dtypes, 6, "outputs are U32 except the peak, which is F32", &fill, &cap));
+    SKR_REQUIRE(!fill || out_offset >= 0, "out_offset must not be negative");
     SKR_TRY(skr_activate(ctx));
     *count = 0;
     if (saw_nan) *saw_nan = 0;
     if (nrows == 0 || col_begin == col_end) return SKR_OK;
-    CellArgs a{(const float*)r->data, r->cols, nrows, col_begin, col_end, row_global0, col_global0, 0, 0, cutoff};
-    a.nseg = (col_end - col_begin + (kCellPer - 1) + kCellSegment - 1) / kCellSegment;
-    a.tiles = nrows * a.nseg;
+    const CellArgs a = cell_tiles(b, cutoff);
     RunArgs ra{seq_of_col ? (const uint32_t*)seq_of_col->data : nullptr, (int)std::min<int64_t>(max_gap, kCellSegment)};
-    void* ws = nullptr;
-    // cells.hip's layout: per-tile counts and a zero behind them, scanned in place; the scan's scratch; the NaN flag
-    const size_t scan_words = skr_radix::scan_scratch_words(a.tiles + 1);
-    SKR_TRY(skr_ctx_workspace(ctx, ((size_t)a.tiles + 1 + scan_words + 1) * 8, &ws));
-    unsigned long long* counts = (unsigned long long*)ws;
-    unsigned long long* total = counts + a.tiles;
-    unsigned* nan_flag = (unsigned*)(total + 1 + scan_words);
-    SKR_HIP(hipMemsetAsync(total, 0, 8, ctx->stream));
-    SKR_HIP(hipMemsetAsync(nan_flag, 0, 8, ctx->stream));
+    SkrCountScan<unsigned long long> cs;  // one count per tile, and the NaN flag
+    SKR_TRY(cs.begin(ctx, a.tiles, true));
     const unsigned grid = (unsigned)std::min<int64_t>(a.tiles, (int64_t)ctx->num_cu * 16);
     {
         SkrProfScope prof(ctx, "runs_count");
-        hipLaunchKernelGGL(runs_count_pass, dim3(grid), dim3(kCellBlock), 0, ctx->stream, a, ra, counts, nan_flag);
+        hipLaunchKernelGGL(runs_count_pass, dim3(grid), dim3(kCellBlock), 0, ctx->stream, a, ra, cs.counts, cs.flag);
         SKR_HIP(hipGetLastError());
     }
-    SKR_TRY(skr_radix::exclusive_scan<unsigned long long>(ctx, counts, a.tiles + 1, total + 1));
-    unsigned long long h_total = 0;
-    unsigned h_nan = 0;
-    SKR_HIP(hipMemcpyAsync(&h_total, total, 8, hipMemcpyDeviceToHost, ctx->stream));
-    SKR_HIP(hipMemcpyAsync(&h_nan, nan_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
-    SKR_HIP(hipStreamSynchronize(ctx->stream));
-    *count = (int64_t)h_total;
-    if (saw_nan) *saw_nan = h_nan ? 1 : 0;
-    if (!fill || h_total == 0) return SKR_OK;
-    if (out_offset > cap || (int64_t)h_total > cap - out_offset) return SKR_OK;  // does not fit: the caller grows its buffers
+    SKR_TRY(cs.finish(ctx, count, saw_nan));
+    if (!fill || *count == 0) return SKR_OK;
+    if (!skr_list_fits(cap, out_offset, *count)) return SKR_OK;  // the caller grows its buffers
     SkrProfScope prof(ctx, "runs_fill");
     RunOut out{(uint32_t*)out_rows->data, (uint32_t*)out_first->data, (uint32_t*)out_last->data, (uint32_t*)out_nhot->data,
                (uint32_t*)out_peak_col->data, (float*)out_peak->data};
-    hipLaunchKernelGGL(runs_fill_pass, dim3(grid), dim3(kCellBlock), 0, ctx->stream, a, ra, counts, (unsigned long long)out_offset, out);
+    hipLaunchKernelGGL(runs_fill_pass, dim3(grid), dim3(kCellBlock), 0, ctx->stream, a, ra, cs.counts, (unsigned long long)out_offset, out);
     SKR_HIP(hipGetLastError());
     return SKR_OK;
 }

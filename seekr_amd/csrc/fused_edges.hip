@@ -7,6 +7,7 @@
 // are the same bits (same kernel arithmetic).
 #include <algorithm>
 
+#include "block.hpp"
 #include "common.hpp"
 #include "edge_pass.hpp"
 #include "radix.hpp"
@@ -38,8 +39,7 @@ extern "C" int skr_pearson_gemm_edges(skr_ctx* ctx, const skr_operand* a, const 
         return skr_set_error(SKR_ERR_UNSUPPORTED, "float32-layout operands take the two-step path (skr_pearson_gemm_op + skr_edges)");
     SKR_REQUIRE(out_rows->dtype == SKR_U32 && out_cols->dtype == SKR_U32 && out_vals->dtype == SKR_F32, "outputs are U32, U32, F32");
     const int64_t M = a->rows, N = b->rows, K = a->cols;
-    SKR_REQUIRE(row_global0 >= 0 && col_global0 >= 0 && row_global0 + M <= 0xffffffffLL && col_global0 + N <= 0xffffffffLL,
-                "global indices must fit 32 bits");
+    SKR_REQUIRE(skr_fits_u32(row_global0, M) && skr_fits_u32(col_global0, N), "global indices must fit 32 bits");
     const bool coherent = a->coherent || b->coherent;
     const int64_t chunk = skr_gemm_chunk_tiles(ctx, coherent);  // the rule the contraction itself applies (knob included)
     const bool multi_chunk = a->kt > chunk;

@@ -15,8 +15,8 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "count_scan.hpp"
 #include "edge_pass.hpp"
-#include "radix.hpp"
 
 namespace {
 
@@ -144,20 +144,12 @@ extern "C" int skr_knn_pairs(skr_ctx* ctx, const skr_mat* idx_a, const skr_mat* 
     if (idx_b)
         SKR_REQUIRE(idx_b->dtype == SKR_U32 && val_b->dtype == SKR_F32 && idx_b->rows == val_b->rows && idx_b->cols == val_b->cols,
                     "idx_b U32 and val_b F32 of one shape");
-    skr_mat* outs[5] = {out_rows, out_cols, out_vals, out_rank_row, out_rank_col};
-    int given = 0;
-    for (skr_mat* m : outs) given += m != nullptr;
-    SKR_REQUIRE(given == 0 || given == 5, "pass all five outputs or none");
+    skr_mat* const outs[5] = {out_rows, out_cols, out_vals, out_rank_row, out_rank_col};
+    const int dtypes[5] = {SKR_U32, SKR_U32, SKR_F32, SKR_U32, SKR_U32};
+    bool given = false;
     int64_t cap = 0;
-    if (given) {
-        SKR_REQUIRE(out_offset >= 0, "out_offset must not be negative");
-        cap = INT64_MAX;
-        for (int i = 0; i < 5; i++) {
-            SKR_REQUIRE(outs[i]->ctx == ctx, "foreign ctx");
-            SKR_REQUIRE(outs[i]->dtype == (i == 2 ? SKR_F32 : SKR_U32), "outputs are U32, U32, F32, U32, U32");
-            cap = std::min(cap, outs[i]->rows * outs[i]->cols);
-        }
-    }
+    SKR_TRY(skr_list_outputs(ctx, outs, dtypes, 5, "outputs are U32, U32, F32, U32, U32", &given, &cap));
+    SKR_REQUIRE(!given || out_offset >= 0, "out_offset must not be negative");
     const int64_t n1 = idx_a->rows, ka = idx_a->cols;
     const int64_t n2 = idx_b ? idx_b->rows : n1, kb = idx_b ? idx_b->cols : 0;
     SKR_REQUIRE(n1 < 0xffffffffLL && n2 < 0xffffffffLL, "rows and columns must stay below 0xFFFFFFFF");
@@ -221,7 +213,7 @@ extern "C" int skr_knn_pairs(skr_ctx* ctx, const skr_mat* idx_a, const skr_mat* 
     SKR_REQUIRE(!h_bad, "a list names an index outside the other set (idx_a: < %lld, idx_b: < %lld)", (long long)n2, (long long)n1);
     *count = (int64_t)h_total;
     if (!given || h_total == 0) return SKR_OK;
-    if (out_offset > cap || (int64_t)h_total > cap - out_offset) return SKR_OK;  // does not fit: the caller grows its buffers
+    if (!skr_list_fits(cap, out_offset, (int64_t)h_total)) return SKR_OK;  // the caller grows its buffers
     SkrProfScope prof(ctx, "knn_pairs_write");
     hipLaunchKernelGGL(pairs_write_kernel, dim3(grid), dim3(256), 0, ctx->stream, lists, (const unsigned long long*)kbuf[cur],
                        (const float*)sbuf[cur], mode, positive_only != 0, (const uint32_t*)marks, (unsigned long long)out_offset,

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "float_key.hpp"
 
 #pragma clang fp contract(off)
 
@@ -395,20 +396,6 @@ __global__ void vec_finish_kernel(float* v, int64_t cols, float n, int take_sqrt
 // ---------------------------------------------------------------------------------------
 // Elementwise: y = post(scale(center(pre(x)))) and the NaN-propagating global minimum of z.
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t order_bits(float f) {  // monotone float -> uint map
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-inline float unorder_bits(uint32_t u) {  // host side inverse
-    const uint32_t b = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
-    union {
-        uint32_t u32;
-        float f32;
-    } cv;
-    cv.u32 = b;
-    return cv.f32;
-}
-
 template <int CK, int SK, bool PRE, bool POST, bool WRITE, bool MIN>
 __global__ __launch_bounds__(256) void elementwise_kernel(const float* __restrict__ x, int64_t rows, int64_t cols,
                                                           const void* __restrict__ center,
@@ -448,7 +435,7 @@ __global__ __launch_bounds__(256) void elementwise_kernel(const float* __restric
         }
     }
     // block reduction of (min, nan)
-    uint32_t enc = order_bits(vmin);
+    uint32_t enc = skr_float_key(vmin);  // the minimum of the keys is the key of the minimum
     uint32_t nanf = any_nan ? 1u : 0u;
     for (int off = 32; off > 0; off >>= 1) {
         const uint32_t o = __shfl_down(enc, off, 64);
@@ -850,7 +837,7 @@ extern "C" int skr_min_nan(skr_ctx* ctx, const skr_mat* x, const skr_mat* center
     SKR_TRY(read_flags(ctx));
     const bool nan = ctx->h_flags[1] != 0;
     if (has_nan) *has_nan = nan ? 1 : 0;
-    if (min_out) *min_out = nan ? NAN : unorder_bits(ctx->h_flags[0]);
+    if (min_out) *min_out = nan ? NAN : skr_float_unkey(ctx->h_flags[0]);
     return SKR_OK;
 }
 

@@ -11,7 +11,9 @@
 // the buffer and the list are sorted together (bitonic, keys with their value bits as payload), the best k become the
 // list and the bound tightens.  Every cell is read once, whatever k is; on rows in random order the number of cells
 // that beat the bound after the first flush is about k ln(width / kTopkStep), so the sorts are few.
+#include "block.hpp"
 #include "common.hpp"
+#include "device_flag.hpp"
 #include "topk_key.hpp"
 
 namespace {
@@ -24,8 +26,7 @@ static_assert((kTopkSort & (kTopkSort - 1)) == 0, "the sort takes a power of two
 static_assert(kTopkStep <= kTopkCap, "an empty buffer must hold one step");
 
 struct TopkArgs {
-    const float* r;
-    int64_t ld, rows, col_begin, col_end, row_global0, col_global0;
+    SkrBlock b;
     int exclude_diag, k, first;
     uint32_t* io_idx;
     float* io_val;
@@ -90,7 +91,7 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(TopkArgs a) {
         __syncthreads();
     };
 
-    for (int64_t i = blockIdx.x; i < a.rows; i += gridDim.x) {
+    for (int64_t i = blockIdx.x; i < a.b.rows; i += gridDim.x) {
         const size_t out0 = (size_t)i * k;
         for (int t = tid; t < k; t += 256) {
             unsigned long long key = 0ull;
@@ -107,20 +108,20 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(TopkArgs a) {
         if (!a.first) flush(0);  // the running list in key order, whatever order it came in
         unsigned long long bound = lkey[k - 1];
 
-        const float* row = a.r + (size_t)i * a.ld;
+        const float* row = a.b.r + (size_t)i * a.b.ld;
         // the sweep starts at the 16-byte boundary at or below the first cell: never below the matrix, since the
         // matrix itself starts on one
-        const int64_t start = a.col_begin - (int64_t)((reinterpret_cast<uintptr_t>(row + a.col_begin) >> 2) & 3);
-        const int64_t ngroups = (a.col_end - start + 3) / 4;
-        const int64_t skip = a.exclude_diag ? a.row_global0 + i - a.col_global0 : -1;  // local column of the diagonal
+        const int64_t start = a.b.col_begin - (int64_t)((reinterpret_cast<uintptr_t>(row + a.b.col_begin) >> 2) & 3);
+        const int64_t ngroups = (a.b.col_end - start + 3) / 4;
+        const int64_t skip = a.exclude_diag ? a.b.row_global0 + i - a.b.col_global0 : -1;  // local column of the diagonal
         int ncand = 0;
         unsigned it = 0;
-        TopkCells cur = topk_load(row, start + 4 * (int64_t)tid, a.col_begin, tid < ngroups ? a.col_end : a.col_begin);
+        TopkCells cur = topk_load(row, start + 4 * (int64_t)tid, a.b.col_begin, tid < ngroups ? a.b.col_end : a.b.col_begin);
         for (int64_t g0 = 0; g0 < ngroups; g0 += 256, it++) {
             const int64_t c0 = start + 4 * (g0 + tid);
             // the next step's cells are on their way while this step is ranked
             const int64_t gn = g0 + 256 + tid;
-            const TopkCells nxt = topk_load(row, start + 4 * gn, a.col_begin, gn < ngroups ? a.col_end : a.col_begin);
+            const TopkCells nxt = topk_load(row, start + 4 * gn, a.b.col_begin, gn < ngroups ? a.b.col_end : a.b.col_begin);
             if (ncand + kTopkStep > kTopkCap) {
                 flush(ncand);
                 ncand = 0;
@@ -134,7 +135,7 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(TopkArgs a) {
                 const int64_t c = c0 + j;
                 const bool in = cur.ok[j] && c != skip;
                 nan_seen = nan_seen || (in && cur.v[j] != cur.v[j]);
-                key[j] = topk_key(cur.v[j], (uint32_t)(a.col_global0 + c));
+                key[j] = topk_key(cur.v[j], (uint32_t)(a.b.col_global0 + c));
                 pass[j] = in && key[j] > bound;
                 mask[j] = __ballot(pass[j]);
                 cnt += (unsigned)__popcll(mask[j]);
@@ -182,39 +183,26 @@ extern "C" int skr_topk_merge_limits(int* kmax, int* candidate_cap) {
 extern "C" int skr_topk_merge_rows(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t col_begin, int64_t col_end,
                                    int64_t row_global0, int64_t col_global0, int exclude_diag, int k, int first,
                                    skr_mat* io_idx, skr_mat* io_val, int* saw_nan) {
-    SKR_REQUIRE(ctx && r && io_idx && io_val, "NULL argument");
-    SKR_REQUIRE(r->ctx == ctx && io_idx->ctx == ctx && io_val->ctx == ctx, "foreign ctx");
-    SKR_REQUIRE(r->dtype == SKR_F32 && io_idx->dtype == SKR_U32 && io_val->dtype == SKR_F32, "r F32, io_idx U32, io_val F32");
-    SKR_REQUIRE(nrows >= 0 && nrows <= r->rows, "nrows out of range");
-    SKR_REQUIRE(col_begin >= 0 && col_begin <= col_end && col_end <= r->cols, "column range out of the matrix");
+    SkrBlock b;  // only columns are written; 0xFFFFFFFF is the index of an unfilled slot
+    SKR_TRY(skr_block(ctx, r, nrows, col_begin, col_end, row_global0, col_global0, SKR_FIT_COLS, &b));
+    SKR_REQUIRE(io_idx && io_val, "NULL argument");
+    SKR_REQUIRE(io_idx->ctx == ctx && io_val->ctx == ctx, "foreign ctx");
+    SKR_REQUIRE(io_idx->dtype == SKR_U32 && io_val->dtype == SKR_F32, "io_idx U32, io_val F32");
     SKR_REQUIRE(k >= 1 && k <= kTopkKmax, "k must be in 1..%d (skr_topk_rows serves a block that stands whole up to 4096)",
                 kTopkKmax);
-    // 0xFFFFFFFF is the index of an unfilled slot
-    SKR_REQUIRE(row_global0 >= 0 && col_global0 >= 0 && col_global0 + col_end <= 0xffffffffLL,
-                "global columns must stay below 0xFFFFFFFF");
     SKR_REQUIRE(io_idx->rows * io_idx->cols >= nrows * k && io_val->rows * io_val->cols >= nrows * k,
                 "the lists must hold %lld cells", (long long)(nrows * k));
     SKR_TRY(skr_activate(ctx));
     if (saw_nan) *saw_nan = 0;
     if (nrows == 0) return SKR_OK;
-    int* d_flag = nullptr;
-    if (saw_nan) {
-        void* ws = nullptr;
-        SKR_TRY(skr_ctx_workspace(ctx, 64, &ws));
-        d_flag = (int*)ws;
-        SKR_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), ctx->stream));
-    }
+    SkrDeviceFlag<int> nan_flag;
+    SKR_TRY(nan_flag.arm(ctx, saw_nan != nullptr));
     {
         SkrProfScope prof(ctx, "topk_merge_rows");
-        const TopkArgs a{(const float*)r->data, r->cols, nrows, col_begin, col_end, row_global0, col_global0,
-                         exclude_diag != 0, k, first != 0, (uint32_t*)io_idx->data, (float*)io_val->data, d_flag};
+        const TopkArgs a{b, exclude_diag != 0, k, first != 0, (uint32_t*)io_idx->data, (float*)io_val->data, nan_flag.d};
         hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)std::min<int64_t>(nrows, (int64_t)ctx->num_cu * 8)), dim3(256), 0,
                            ctx->stream, a);
         SKR_HIP(hipGetLastError());
     }
-    if (saw_nan) {
-        SKR_HIP(hipMemcpyAsync(saw_nan, d_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        SKR_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return SKR_OK;
+    return nan_flag.read(ctx, saw_nan);  // no flag asked for: no wait for the device
 }

@@ -21,7 +21,9 @@
 //
 // LDS: lists 32 x 65 x (8 + 4) bytes, segments the same (the pitch of 65 entries spreads the 32 columns of a half wave
 // over the banks when they append at the same depth), 32 counters: 48.9 KiB, three workgroups per CU.
+#include "block.hpp"
 #include "common.hpp"
+#include "device_flag.hpp"
 #include "topk_key.hpp"
 
 namespace {
@@ -36,8 +38,7 @@ static_assert(kColsStep <= kColsCap, "an empty segment must hold one step");
 static_assert(kColsStrip * 8 == 256 && kColsStep == 16, "thread t: column t & 31, rows t >> 5 and (t >> 5) + 8");
 
 struct ColsArgs {
-    const float* r;
-    int64_t ld, rows, col_begin, col_end, row_global0, col_global0;
+    SkrBlock b;
     int exclude_diag, k, first;
     uint32_t* io_idx;
     float* io_val;
@@ -85,7 +86,7 @@ __global__ __launch_bounds__(256) void topk_cols_kernel(ColsArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, k = a.k;
     const int c = tid & (kColsStrip - 1), slot = tid >> 5;  // this thread's column of the strip, and its row of a step
     constexpr int kPerWave = kColsStrip / 4;                // columns a wave merges
-    const int64_t strips = (a.col_end - a.col_begin + kColsStrip - 1) / kColsStrip;
+    const int64_t strips = (a.b.col_end - a.b.col_begin + kColsStrip - 1) / kColsStrip;
     bool nan_seen = false;
 
     // every column's candidates into its list (every thread calls it; wave w serves columns w * 8 ... w * 8 + 7)
@@ -110,14 +111,14 @@ __global__ __launch_bounds__(256) void topk_cols_kernel(ColsArgs a) {
     };
 
     for (int64_t s = blockIdx.x; s < strips; s += gridDim.x) {
-        const int64_t j0 = a.col_begin + s * kColsStrip;  // the strip's first column in r
-        const int ncols = (int)std::min<int64_t>(kColsStrip, a.col_end - j0);
+        const int64_t j0 = a.b.col_begin + s * kColsStrip;  // the strip's first column in r
+        const int ncols = (int)std::min<int64_t>(kColsStrip, a.b.col_end - j0);
         for (int q = 0; q < kPerWave; q++) {
             const int cc = wave * kPerWave + q;
             ColsEntry e{0ull, 0u};
             if (!a.first) {  // the running list in key order, whatever order it came in
                 if (cc < ncols && lane < k) {
-                    const size_t at = (size_t)(j0 - a.col_begin + cc) * k + lane;
+                    const size_t at = (size_t)(j0 - a.b.col_begin + cc) * k + lane;
                     const uint32_t idx = a.io_idx[at];
                     const float v = a.io_val[at];
                     e.val = __float_as_uint(v);
@@ -133,29 +134,29 @@ __global__ __launch_bounds__(256) void topk_cols_kernel(ColsArgs a) {
 
         const bool col_ok = c < ncols;
         const int64_t jc = j0 + c;
-        const int64_t skip = a.exclude_diag ? a.col_global0 + jc - a.row_global0 : -1;  // local row of the diagonal
-        const float* col = a.r + jc;
+        const int64_t skip = a.exclude_diag ? a.b.col_global0 + jc - a.b.row_global0 : -1;  // local row of the diagonal
+        const float* col = a.b.r + jc;
         float cur[2], nxt[2];
 #pragma unroll
         for (int h = 0; h < 2; h++) {
             const int64_t i = slot + 8 * h;
-            cur[h] = col_ok && i < a.rows ? col[(size_t)i * a.ld] : 0.f;
+            cur[h] = col_ok && i < a.b.rows ? col[(size_t)i * a.b.ld] : 0.f;
         }
-        for (int64_t i0 = 0; i0 < a.rows; i0 += kColsStep) {
+        for (int64_t i0 = 0; i0 < a.b.rows; i0 += kColsStep) {
             // the next step's cells are on their way while this step is ranked
 #pragma unroll
             for (int h = 0; h < 2; h++) {
                 const int64_t i = i0 + kColsStep + slot + 8 * h;
-                nxt[h] = col_ok && i < a.rows ? col[(size_t)i * a.ld] : 0.f;
+                nxt[h] = col_ok && i < a.b.rows ? col[(size_t)i * a.b.ld] : 0.f;
             }
             int crowded = 0;
 #pragma unroll
             for (int h = 0; h < 2; h++) {
                 const int64_t i = i0 + slot + 8 * h;
-                const bool in = col_ok && i < a.rows && i != skip;
+                const bool in = col_ok && i < a.b.rows && i != skip;
                 const float v = cur[h];
                 nan_seen = nan_seen || (in && v != v);
-                const unsigned long long key = topk_key(v, (uint32_t)(a.row_global0 + i));
+                const unsigned long long key = topk_key(v, (uint32_t)(a.b.row_global0 + i));
                 if (in && key > bound) {
                     // before a step no segment holds more than kColsCap - kColsStep entries, and a step adds at most
                     // kColsStep to a column: pos < kColsCap
@@ -174,7 +175,7 @@ __global__ __launch_bounds__(256) void topk_cols_kernel(ColsArgs a) {
         for (int q = 0; q < kPerWave; q++) {
             const int cc = wave * kPerWave + q;
             if (cc < ncols && lane < k) {
-                const size_t at = (size_t)(j0 - a.col_begin + cc) * k + lane;
+                const size_t at = (size_t)(j0 - a.b.col_begin + cc) * k + lane;
                 const unsigned long long key = lkey[cc][lane];
                 a.io_idx[at] = key ? 0xFFFFFFFFu - (uint32_t)key : 0xFFFFFFFFu;
                 a.io_val[at] = __uint_as_float(key ? lval[cc][lane] : 0x7FC00000u);
@@ -198,40 +199,27 @@ extern "C" int skr_topk_merge_cols_limits(int* kmax, int* strip_cols, int* rows_
 extern "C" int skr_topk_merge_cols(skr_ctx* ctx, const skr_mat* r, int64_t nrows, int64_t col_begin, int64_t col_end,
                                    int64_t row_global0, int64_t col_global0, int exclude_diag, int k, int first,
                                    skr_mat* io_idx, skr_mat* io_val, int* saw_nan) {
-    SKR_REQUIRE(ctx && r && io_idx && io_val, "NULL argument");
-    SKR_REQUIRE(r->ctx == ctx && io_idx->ctx == ctx && io_val->ctx == ctx, "foreign ctx");
-    SKR_REQUIRE(r->dtype == SKR_F32 && io_idx->dtype == SKR_U32 && io_val->dtype == SKR_F32, "r F32, io_idx U32, io_val F32");
-    SKR_REQUIRE(nrows >= 0 && nrows <= r->rows, "nrows out of range");
-    SKR_REQUIRE(col_begin >= 0 && col_begin <= col_end && col_end <= r->cols, "column range out of the matrix");
+    SkrBlock b;  // rows are written, and 0xFFFFFFFF is the index of an unfilled slot; columns as in skr_topk_merge_rows
+    SKR_TRY(skr_block(ctx, r, nrows, col_begin, col_end, row_global0, col_global0, SKR_FIT_BOTH, &b));
+    SKR_REQUIRE(io_idx && io_val, "NULL argument");
+    SKR_REQUIRE(io_idx->ctx == ctx && io_val->ctx == ctx, "foreign ctx");
+    SKR_REQUIRE(io_idx->dtype == SKR_U32 && io_val->dtype == SKR_F32, "io_idx U32, io_val F32");
     SKR_REQUIRE(k >= 1 && k <= kColsKmax, "k must be in 1..%d (the column lists are one slot per lane of a wave)", kColsKmax);
-    // 0xFFFFFFFF is the index of an unfilled slot
-    SKR_REQUIRE(row_global0 >= 0 && col_global0 >= 0 && row_global0 + nrows <= 0xffffffffLL &&
-                    col_global0 + col_end <= 0xffffffffLL, "global rows and columns must stay below 0xFFFFFFFF");
     const int64_t width = col_end - col_begin;
     SKR_REQUIRE(io_idx->rows * io_idx->cols >= width * k && io_val->rows * io_val->cols >= width * k,
                 "the lists must hold %lld cells", (long long)(width * k));
     SKR_TRY(skr_activate(ctx));
     if (saw_nan) *saw_nan = 0;
     if (width == 0) return SKR_OK;
-    int* d_flag = nullptr;
-    if (saw_nan) {
-        void* ws = nullptr;
-        SKR_TRY(skr_ctx_workspace(ctx, 64, &ws));
-        d_flag = (int*)ws;
-        SKR_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), ctx->stream));
-    }
+    SkrDeviceFlag<int> nan_flag;
+    SKR_TRY(nan_flag.arm(ctx, saw_nan != nullptr));
     {
         SkrProfScope prof(ctx, "topk_merge_cols");
-        const ColsArgs a{(const float*)r->data, r->cols, nrows, col_begin, col_end, row_global0, col_global0,
-                         exclude_diag != 0, k, first != 0, (uint32_t*)io_idx->data, (float*)io_val->data, d_flag};
+        const ColsArgs a{b, exclude_diag != 0, k, first != 0, (uint32_t*)io_idx->data, (float*)io_val->data, nan_flag.d};
         const int64_t strips = (width + kColsStrip - 1) / kColsStrip;
         hipLaunchKernelGGL(topk_cols_kernel, dim3((unsigned)std::min<int64_t>(strips, (int64_t)ctx->num_cu * 4)), dim3(256), 0,
                            ctx->stream, a);
         SKR_HIP(hipGetLastError());
     }
-    if (saw_nan) {
-        SKR_HIP(hipMemcpyAsync(saw_nan, d_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        SKR_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return SKR_OK;
+    return nan_flag.read(ctx, saw_nan);  // no flag asked for: no wait for the device
 }
